@@ -41,17 +41,29 @@ the timed region.
   BASELINE config 4), one tile per rank, gathered and assembled likewise.
 --gather radiance: the float radiance (the sqrt'd colour before
   quantisation) is gathered beside the RGBA8 frame.
-Afterwards rank 0 checks the last assembled frames (and radiance) against
-the same frames traced on its GPU alone (config.frames_verified) and times
-those (single_gpu, speedup_vs_1gpu); every rank reports its trace and
-exchange device time (per_rank).
+Every rank reports its trace and exchange device time (per_rank).
+
+A plain run sets up, counts the timed frames' segments, settles and warms up,
+times the K steps and prints the JSON line.  --dump-outputs DIR also writes
+the last timed step's frame as rank 0 holds it (DIR/rgba.npy, H x W x 4, and
+DIR/radiance.npy with --gather radiance) in float32 (dump_array); the scene,
+the cameras of the timed frames and so these arrays are the same from run to
+run.  Everything below that takes GPU or CPU runs of its own is measured only
+with --full and is null without it: config.frames_verified, single_gpu,
+lane_utilisation, camera_stop, cpu_baseline, pcie.
+
+--full: afterwards rank 0 checks the last assembled frames (and radiance)
+against the same frames traced on its GPU alone (config.frames_verified; N = 1:
+the frames the timed loop left in its slots) and at N > 1 times those
+(single_gpu, speedup_vs_1gpu).
 
 --camera-path orbit: every frame has its own camera (the default camera's
 origin orbiting the look-at point, 0.5 degrees per frame, as the app's
 camera moves between frames, VulkanApp.java:726-770); segments are counted
-per camera.  After the timed frames the camera stops and the first frames
-at rest (the learning frame of the heavy-first order among them) are timed
-one by one (camera_stop).
+per camera, and the timed frames' cameras count from the first timed frame.
+--full: after the timed frames the camera stops and the first frames at rest
+(the learning frame of the heavy-first order among them) are timed one by
+one (camera_stop).
 
 value = segments of the K timed frames / wall time of the timed steps (max
 over ranks), in millions.  A segment is one executed bounce-loop iteration
@@ -73,12 +85,12 @@ HBM and the L2 peaks (the scene stays in L2 / MALL: those bytes are mostly
 cache hits), the measured HBM rate (PMC bytes / frame_ms_device), the
 vector-memory issue rate (SQ_INSTS_VMEM_RD against a floor measured by
 tools/ubench/ta_cost.hip, a builder's microbenchmark, not a guide figure) and
-the lockstep walk's lane utilisation (a diagnostic launch outside the timed
-region: the lanes' own walk steps / (64 x the waves' lockstep steps)).
-cpu_baseline: the CPU oracle (oracle/rt_oracle.c, OpenMP) on a bounded row
+the lockstep walk's lane utilisation (--full; a diagnostic launch outside the
+timed region: the lanes' own walk steps / (64 x the waves' lockstep steps)).
+cpu_baseline (--full): the CPU oracle (oracle/rt_oracle.c, OpenMP) on a bounded row
 sample of the same frame, rank 0 at N = 1 only (the reference has no CPU
 render path: BVHNode.hit throws, BVHNode.java:35-41).
-pcie (N = 1): rt_render_async with 4 frames in flight into pinned host
+pcie (--full, N = 1): rt_render_async with 4 frames in flight into pinned host
 frames, every frame read back over PCIe (the rate a host that displays the
 frames sees; never `value`).
 """
@@ -225,6 +237,25 @@ def file_sha16(path: str) -> str:
     import hashlib
     with open(path, "rb") as fh:
         return hashlib.sha256(fh.read()).hexdigest()[:16]
+
+
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: all files together
+DUMP_SEED = 20240607
+
+
+def dump_array(path: str, a, max_bytes: int) -> None:
+    """--dump-outputs: array a as float32 in path (.npy), whole (its own
+    shape) when that fits max_bytes, else the elements at max_bytes / 4 flat
+    indices drawn without replacement by numpy's default_rng(DUMP_SEED) and
+    sorted (a 1-D file; the indices depend on a's size alone, so two builds
+    write the same elements)."""
+    import numpy as np
+    a = np.ascontiguousarray(a)
+    keep = (max_bytes - 128) // 4                      # 128: the .npy header
+    if a.size > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=keep, replace=False))
+        a = a.reshape(-1)[idx]
+    np.save(path, a.astype(np.float32))
 
 
 # ---- rank launcher -----------------------------------------------------------
@@ -398,10 +429,21 @@ def main() -> None:
                          "and the closing device synchronisation joins them; join = they also wait on / are joined "
                          "into the main stream around the region (two cross-queue hops)")
     ap.add_argument("--set", default="", help="schedule options name=value,... (rt_set_option) before timing")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-lanes", action="store_true", help="skip the lane-utilisation diagnostic launch")
-    ap.add_argument("--no-single", action="store_true", help="N > 1: skip rank 0's one-GPU timing")
-    ap.add_argument("--no-pcie", action="store_true", help="N = 1: skip the PCIe-inclusive rt_render_async rate")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure, each in runs of its own outside the timed "
+                         "region: the frames checked against the same frames traced whole (config.frames_verified), "
+                         "the lane-utilisation diagnostic launch, the CPU baseline, the PCIe-inclusive rate, the "
+                         "camera-stop frames (orbit) and at N > 1 rank 0's one-GPU timing (the --no-* options "
+                         "drop single ones of them); without it these fields are null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the frame a caller of the "
+                         "timed path receives: rgba, and radiance where it is gathered) as DIR/<name>.npy in "
+                         "float32 (dump_array: at most 64 MB in all, a fixed seeded sample of a larger output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-lanes", action="store_true", help="--full: skip the lane-utilisation diagnostic launch")
+    ap.add_argument("--no-single", action="store_true", help="--full, N > 1: skip rank 0's one-GPU timing")
+    ap.add_argument("--no-pcie", action="store_true",
+                    help="--full, N = 1: skip the PCIe-inclusive rt_render_async rate")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU baseline sample time")
     ap.add_argument("--settle-max", type=int, default=3000, help="at most this many settle launches")
     ap.add_argument("--pcie-warm", type=int, default=200,
@@ -498,7 +540,7 @@ def main() -> None:
     # (in the middle of bench.py they did: 0.49 vs 0.36 ms per frame,
     # profiles/r03/emulation/r3l pipeline.jsonl vs bench20_pcie.json).
     pcie = None
-    if rank == 0 and not dist_on and args.camera_path == "static" and not args.no_pcie:
+    if args.full and rank == 0 and not dist_on and args.camera_path == "static" and not args.no_pcie:
         pcie = pcie_rate(renderer, cfg.camera(), W, H, B, warm=args.pcie_warm)
 
     # ---- partition -------------------------------------------------------
@@ -615,9 +657,13 @@ def main() -> None:
     cam_cache = {}
     cam_arrays = {}
 
+    cam_first = {"k": 0}   # the first timed frame (set once the settle launches are counted)
+
     def cam_of(k):
-        if args.camera_path == "static":
-            k = 0
+        # the moving camera's positions count from the first timed frame: the
+        # number of settle launches follows the clock, the timed frames' cameras
+        # (and so --dump-outputs) must not
+        k = 0 if args.camera_path == "static" else k - cam_first["k"]
         c = cam_cache.get(k)
         if c is None:
             c = cam_cache[k] = camera_path(cfg, args.camera_path, 1, k)[0]
@@ -1017,6 +1063,9 @@ def main() -> None:
         dist.all_reduce(n_settle, op=dist.ReduceOp.MIN)
     n_settle = int(n_settle.item()) * F
     k_t0 = after(after(0, n_settle), W_fr)
+    cam_first["k"] = k_t0
+    cam_cache.clear()
+    cam_arrays.clear()
     if mode == "spans":
         if args.camera_path == "static" and plan.batch(1) is plan:   # every batch the same span
             one = count_frames([k_t0])[0]
@@ -1109,6 +1158,25 @@ def main() -> None:
     elapsed = time.perf_counter() - t_start
     gc.enable()
     pk_timed = renderer.get_option("plain_kernels")
+    if args.dump_outputs and rank == 0:
+        # the last timed step's frame, as the timed loop left it (before anything
+        # below traces again)
+        outs = {}
+        if mode == "whole":
+            k0, n = slot_last[(st["j"] - 1) % D]         # the last launch's slot; its last frame
+            outs["rgba"] = rgba_slots[(st["j"] - 1) % D][(n - 1) * H:n * H]
+        elif last["rgba"] is not None:
+            outs["rgba"] = last["rgba"][-1].reshape(H, W, 4)
+            if last["rad"] is not None:
+                outs["radiance"] = last["rad"][-1].reshape(H, W, 3)
+        if not outs:
+            raise SystemExit("--dump-outputs: this run assembles no frames (BENCH_EMULATE)")
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        # whole arrays when all of them fit the limit together, else equal shares of it
+        fits = sum(a.numel() * 4 + 128 for a in outs.values()) <= DUMP_MAX_BYTES
+        for name, a in outs.items():
+            dump_array(os.path.join(args.dump_outputs, name + ".npy"), a.cpu().numpy(),
+                       DUMP_MAX_BYTES if fits else DUMP_MAX_BYTES // len(outs))
     n_launch = len(evs)
     launch_ms = float(np.mean([a.elapsed_time(b) for (a, b), _ in evs]))
     region_ms = (max(reg[0].elapsed_time(e) for e in ends) if lean else reg[0].elapsed_time(reg[1]))
@@ -1138,10 +1206,10 @@ def main() -> None:
     heavy_used = renderer.get_option("heavy_tiles_used")   # of the last timed launch
     heavy_px_used = renderer.get_option("heavy_pixels_used")
     lanes = lane_utilisation(renderer, L, ctx, lambda: trace(k_t0, 1, main_stream, count_rgba.data_ptr(), None),
-                             dev) if not (args.no_lanes or mode == "spans") else None
+                             dev) if args.full and not (args.no_lanes or mode == "spans") else None
     verified = None
     single = None
-    if dist_on and not emu and rank == 0 and last["rgba"] is not None:
+    if args.full and dist_on and not emu and rank == 0 and last["rgba"] is not None:
         # the assembled frames (and radiance) equal the frames traced whole on one GPU
         ok = True
         full = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
@@ -1181,7 +1249,7 @@ def main() -> None:
             renderer.set_option("concurrent_launches", D)
 
     gpu_frame = None
-    if mode == "whole" and rank == 0:
+    if args.full and mode == "whole" and rank == 0:
         # N = 1: the frames the timed loop left in its slots (the last launch of
         # every stream) equal the same frames traced whole, one launch at a time
         # on one stream (rt_render_tile_device)
@@ -1200,7 +1268,7 @@ def main() -> None:
     # the camera stops (orbit): the first frames at rest, timed one by one (the
     # first repeat of a camera learns its own heavy-first order)
     stop = None
-    if args.camera_path != "static" and mode != "spans":
+    if args.full and args.camera_path != "static" and mode != "spans":
         k_last = k_t0 + K - 1
         ms = []
         for i in range(8):
@@ -1237,7 +1305,7 @@ def main() -> None:
     roof = roofline(pmc, alg_bytes, ref_layout_bytes, l_seg, launch_ms, frame_ms, n_cu, lanes, walk_mb)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(built, cam_of(k_t0), W, H, B, segments / K, args.cpu_seconds, gpu_frame)
 
     # production kernels enqueued after the timed region (verification, camera
@@ -1281,6 +1349,7 @@ def main() -> None:
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             # the series this run belongs to (at N = 1 weak and strong are the same work)

@@ -9,8 +9,6 @@ for p in (PKG_DIR, ROOT):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-REFERENCE = "/root/reference"
-
 # A Renderer that does not choose otherwise walks the reference's own tree
 # (option accel 0, whose work counters are the oracle's own; rt_create reads
 # RTAMD_ACCEL).  The default accel walk (SAH tree) runs in
@@ -67,10 +65,3 @@ def renderer():
     r = rtamd.Renderer((0,))
     yield r
     r.close()
-
-
-def reference_path(*parts):
-    p = os.path.join(REFERENCE, *parts)
-    if not os.path.exists(p):
-        pytest.skip("reference checkout not present")
-    return p

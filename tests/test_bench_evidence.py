@@ -111,6 +111,29 @@ def test_default_schedule_helpers():
     assert bench.default_root_weight(1) == 1.0
 
 
+def test_dump_array(tmp_path):
+    """--dump-outputs: float32 files; an array within the budget keeps its
+    shape and values, a larger one is the elements at seeded, sorted flat
+    indices that depend on its size alone, and the file stays in the budget."""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    a = rng.integers(0, 256, (7, 9, 4), dtype=np.uint8)
+    p = str(tmp_path / "a.npy")
+    bench.dump_array(p, a, 1 << 20)
+    got = np.load(p)
+    assert got.dtype == np.float32 and got.shape == a.shape and np.array_equal(got, a)
+    budget = 4096
+    b = rng.standard_normal(5000).astype(np.float32).reshape(50, 100)
+    bench.dump_array(p, b, budget)
+    s1 = np.load(p)
+    assert os.path.getsize(p) <= budget and s1.dtype == np.float32 and s1.ndim == 1
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(b.size, size=s1.size, replace=False))
+    assert np.array_equal(s1, b.reshape(-1)[idx])
+    bench.dump_array(p, b + 1.0, budget)                     # another build's values: the same elements
+    assert np.array_equal(np.load(p), (b + 1.0).reshape(-1)[idx])
+    assert bench.DUMP_MAX_BYTES <= 64 * 10**6
+
+
 def _r04(session, name):
     with open(os.path.join(R04, session, name)) as fh:
         return json.loads([x for x in fh if x.startswith("{")][-1])

@@ -1,13 +1,13 @@
 """Host scene pipeline (CPU): the product's C++ builder vs the Python
 restatement of the Java code (oracle/scene_oracle.py), byte for byte."""
+import gzip
+import hashlib
 import json
 import os
 import random
 
 import numpy as np
 import pytest
-
-from conftest import reference_path
 
 
 def _load_json(path):
@@ -17,6 +17,23 @@ def _load_json(path):
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = _load_json(os.path.join(HERE, "golden", "golden.json"))
+
+# SHA-256 of the reference's objects/*.obj, whose copies are the fixtures
+# under tests/golden/ (FinalBaseMesh.obj gzip'd)
+REFERENCE_OBJ_SHA256 = {
+    "cube.obj": "faa37386415fbf50c85b610a41386dc5687c730077791e85295be7b5a5c93702",
+    "ground_plane.obj": "86e0a2af7da648c8526047147aacb9f7ca08e684b3f0386e6156d70865a1c807",
+    "FinalBaseMesh.obj": "85071a35755ddf9eda32a9beb27a3e36b364bab2ad8942243138f943f27acb23",
+}
+
+
+def _golden_obj_bytes(name):
+    path = os.path.join(HERE, "golden", name)
+    if os.path.exists(path):
+        with open(path, "rb") as f:
+            return f.read()
+    with gzip.open(path + ".gz", "rb") as f:
+        return f.read()
 
 
 def _oracle_build(verts, mats, seed):
@@ -160,14 +177,20 @@ def test_procedural_mesh():
     assert np.array_equal(a, b)
 
 
-def test_obj_loader_on_reference_assets():
-    """SceneBuilder.loadModel inputs: the reference's own OBJ files (read when
-    the reference checkout is present; the configs embed the same triangles)."""
+def test_obj_loader_on_reference_assets(tmp_path):
+    """SceneBuilder.loadModel inputs: the reference's own OBJ files, stored
+    unchanged as fixtures under tests/golden/ (FinalBaseMesh.obj gzip'd; the
+    SHA-256 of each is the reference file's); the configs embed the same
+    triangles."""
     from rtamd import Mesh
     from rtamd.configs import cube_mesh, plane_mesh
-    assert np.array_equal(Mesh.load_obj(reference_path("objects", "cube.obj")).tris, cube_mesh().tris)
-    assert np.array_equal(Mesh.load_obj(reference_path("objects", "ground_plane.obj")).tris, plane_mesh().tris)
-    fbm = Mesh.load_obj(reference_path("objects", "FinalBaseMesh.obj"))
+    for name, sha in REFERENCE_OBJ_SHA256.items():
+        assert hashlib.sha256(_golden_obj_bytes(name)).hexdigest() == sha, name
+    assert np.array_equal(Mesh.load_obj(os.path.join(HERE, "golden", "cube.obj")).tris, cube_mesh().tris)
+    assert np.array_equal(Mesh.load_obj(os.path.join(HERE, "golden", "ground_plane.obj")).tris, plane_mesh().tris)
+    p = tmp_path / "FinalBaseMesh.obj"
+    p.write_bytes(_golden_obj_bytes("FinalBaseMesh.obj"))
+    fbm = Mesh.load_obj(str(p))
     assert len(fbm) == 48_918                   # 24,459 quads -> 2 triangles each
     lo, hi = fbm.tris.min(axis=(0, 1)), fbm.tris.max(axis=(0, 1))
     assert np.allclose(lo, [-5.8425, -0.0566, -1.8531]) and np.allclose(hi, [5.8425, 20.6841, 1.9170])
@@ -217,11 +240,9 @@ def test_final_base_mesh_fixture():
     flat = built.triangle_count
     assert flat == 65_096
     assert built.flat_bvh_data.nbytes == 48 * (2 * flat - 1)
-    from conftest import REFERENCE
-    src = os.path.join(REFERENCE, "objects", "FinalBaseMesh.obj")
-    if os.path.exists(src):                     # the fixture is the reference's file, unchanged
-        from rtamd import Mesh
-        assert np.array_equal(Mesh.load_obj(src).tris, m.tris)
+    # the fixture is the reference's file, unchanged
+    assert hashlib.sha256(_golden_obj_bytes("FinalBaseMesh.obj")).hexdigest() == \
+        REFERENCE_OBJ_SHA256["FinalBaseMesh.obj"]
 
 
 def _obj_text(rng, n_polys=60):

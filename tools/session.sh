@@ -49,7 +49,7 @@ run() {  # run NAME SECONDS CMD...
 prof() {  # prof CONFIG STEPS
   local c=$1 k=$2 d="$OUT/prof$1"
   run "prof$c" 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -o run -- \
-      python3 bench.py --config "$c" --steps "$k" --warmup 5 --no-cpu-baseline --no-pcie > "$OUT/prof$c.json" 2> "$OUT/prof$c.err"
+      python3 bench.py --full --config "$c" --steps "$k" --warmup 5 --no-cpu-baseline --no-pcie > "$OUT/prof$c.json" 2> "$OUT/prof$c.err"
   local tr
   tr=$(find "$d" -name "run_kernel_trace.csv" | head -n 1)
   python3 tools/rocprof_union.py "$tr" --steps "$k" --bench "$OUT/prof$c.json" --out "$OUT/union_cfg$c.json" \
@@ -75,8 +75,8 @@ for s in "$@"; do
     test)     run pytest 1200 python -u -m pytest tests -m gpu -q -rA --timeout 120 --timeout-method thread \
                   > "$OUT/pytest_gpu.log" 2>&1 ;;
     smoke)    run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 ;;
-    bench)    run bench 600 python bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
-    bench200) run bench200 600 python bench.py > "$OUT/bench200.json" 2> "$OUT/bench200.err" ;;
+    bench)    run bench 600 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+    bench200) run bench200 600 python bench.py --full > "$OUT/bench200.json" 2> "$OUT/bench200.err" ;;
     prof3)    prof 3 20 ;;
     prof5)    prof 5 10 ;;
     # record keys: bench.py pmc_key (the default accel 8 walk: "@accel8"; the N = 1 default of 4 frames per launch: "@f4")
@@ -87,23 +87,23 @@ for s in "$@"; do
     fetch5)   pmc 5 cfg5_1M_3840x2160_b8@nocoop@accel8@f4 n "--set coop_lanes=0" && \
               pmc 5 cfg5_1M_3840x2160_b8@split40@accel8@f4 s "--set order_split=40" ;;
     pmc3o)    pmc 3 cfg3_50k_1920x1080_b4@orbit@accel8 o "--camera-path orbit --batch 1" ;;
-    orbit)    run orbit 600 python bench.py --steps 20 --warmup 5 --camera-path orbit \
+    orbit)    run orbit 600 python bench.py --full --steps 20 --warmup 5 --camera-path orbit \
                   > "$OUT/bench_orbit.json" 2> "$OUT/bench_orbit.err" ;;
     cfgs)     for a in "4 50" "5 10" "6 200"; do
                 set -- $a
-                run "cfg$1" 300 python bench.py --config "$1" --steps "$2" --warmup 3 --no-cpu-baseline \
+                run "cfg$1" 300 python bench.py --full --config "$1" --steps "$2" --warmup 3 --no-cpu-baseline \
                     > "$OUT/bench_cfg$1.json" 2> "$OUT/bench_cfg$1.err"
               done ;;
     inflight) for k in ${INFLIGHT:-1 2 4}; do
-                run "inflight$k" 300 python bench.py --inflight "$k" --steps 200 --warmup 5 --no-cpu-baseline \
+                run "inflight$k" 300 python bench.py --full --inflight "$k" --steps 200 --warmup 5 --no-cpu-baseline \
                     --no-pcie > "$OUT/bench_if$k.json" 2> "$OUT/bench_if$k.err"
               done ;;
     share)    run share 600 python tools/share_inflight_bench.py ${SHARE_ARGS:-} > "$OUT/share.jsonl" 2> "$OUT/share.err" ;;
     emu)      run emu 900 python tools/rank_emulator.py ${EMU_ARGS:-} > "$OUT/emu.jsonl" 2> "$OUT/emu.err" ;;
     pipeline) run pipeline 300 python tools/pipeline_bench.py ${PIPE_ARGS:-} > "$OUT/pipeline.jsonl" 2> "$OUT/pipeline.err" ;;
-    spawn2)   run spawn2 600 env BENCH_SHARE_GPU=1 BENCH_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 20 \
+    spawn2)   run spawn2 600 env BENCH_SHARE_GPU=1 BENCH_DIST_BACKEND=gloo python bench.py --full --gpus 2 --steps 20 \
                   --warmup 5 > "$OUT/spawn2.json" 2> "$OUT/spawn2.err" ;;
-    spawn4)   run spawn4 600 env BENCH_SHARE_GPU=1 BENCH_DIST_BACKEND=gloo python bench.py --gpus 4 --steps 10 \
+    spawn4)   run spawn4 600 env BENCH_SHARE_GPU=1 BENCH_DIST_BACKEND=gloo python bench.py --full --gpus 4 --steps 10 \
                   --warmup 3 --partition tiles --gather radiance > "$OUT/spawn4.json" 2> "$OUT/spawn4.err" ;;
     ab3)      run ab3 900 bash tools/ab_old_new.sh "$OUT/ab3" 3 --steps 200 --warmup 5 ;;
     ab5)      run ab5 900 bash tools/ab_old_new.sh "$OUT/ab5" 2 --config 5 --steps 10 --warmup 3 ;;
