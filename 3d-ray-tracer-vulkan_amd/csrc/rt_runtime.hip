@@ -223,35 +223,6 @@ int build_host_scene(const void* vertices, size_t vertex_bytes,
 using namespace rtamd;
 
 static constexpr int kMaxSlots = 8;   // rt_render_async frame slots per device
-// Walk records with no leaf straddling a 128-B line (option leaf_align; 2 =
-// auto: aligned when the packed records exceed kWin32Bytes, like the window
-// size): config 5 8.24 vs 8.39-8.46 ms and 21.3 vs 22.4 GB fetched per frame
-// (profiles/r04/r4g), for 11% more slots.  A scene whose records stay in L2
-// gains nothing from it, and its kernels then skip the pad-bit arithmetic
-// (kFeatPad off: config 3 0.303-0.304 vs 0.306-0.307 ms, profiles/r04/r4m).
-#ifndef RT_LEAF_ALIGN
-#define RT_LEAF_ALIGN 2
-#endif
-// Option accel's default: the binned-SAH tree in 8 octant
-// layouts.  Config 3 0.1279-0.1288 ms per frame against 0.2962-0.2964 for the
-// reference's tree and order, config 5 1.24-1.25 against 7.84 ms, config 6
-// 0.140 against 0.342 (profiles/r05/r5a, r5b); 1 layout: 0.1365, 1.40, 0.148.
-#ifndef RT_ACCEL
-#define RT_ACCEL 8
-#endif
-// Option accel_half's default: the accel records' internal boxes in half
-// precision (accel_build.h format 1).
-#ifndef RT_ACCEL_HALF
-#define RT_ACCEL_HALF 0
-#endif
-// Option accel_wide's default: the 4-wide tree (accel_build.h format 2).
-#ifndef RT_ACCEL_WIDE
-#define RT_ACCEL_WIDE 0
-#endif
-// Option split_bounce's default.
-#ifndef RT_SPLIT_BOUNCE
-#define RT_SPLIT_BOUNCE 0
-#endif
 
 struct PerDevice {
     int          device = 0;
@@ -347,7 +318,7 @@ static constexpr size_t kWin32Bytes = 32ull << 20;
 // option split_bounce: the largest ray-slot allocation per launch stream
 static constexpr size_t kSplitSlotBytes = 256ull << 20;
 // The walk's buffer loads address the records with 32-bit byte offsets
-// (rt_trace.hip, RT_CHAIN 2): at most 2^27 - 4 slots of 32 B (~45M triangles).
+// (rt_trace.hip wbuf): at most 2^27 - 4 slots of 32 B (~45M triangles).
 static constexpr unsigned kMaxWalkSlots = (1u << 27) - 4;
 static constexpr size_t kDiagWords = 8;   // per-wave diag record (rt_trace.hip, rtamd.h rt_diag_copy)
 
@@ -421,13 +392,25 @@ struct rt_ctx {
     int  xcd_order = 0;            // device-learned orders: XCD c takes one class of row bands (rt_learn.hip;
                                    //   the band height in wave-tile rows, 0 = off)
     int  learn_device = 1;         // heavy_first: learn the order on the device (rt_learn.hip; 0 = on the host)
-    int  leaf_align = RT_LEAF_ALIGN;   // walk records: no leaf straddles a 128-B line (a pad slot before it)
-    int  accel_half = RT_ACCEL_HALF;   // at the next upload: accel records in format 1 (accel_build.h)
-    int  accel_wide = RT_ACCEL_WIDE;   // at the next upload: the 4-wide tree, format 2 (overrides accel_half)
-    int  split_bounce = RT_SPLIT_BOUNCE;   // accel walk: paths alive at this bounce finish in a second kernel
+    // Walk records with no leaf straddling a 128-B line (a pad slot before it;
+    // 2 = auto: aligned when the packed records exceed kWin32Bytes, like the
+    // window size): config 5 8.24 vs 8.39-8.46 ms and 21.3 vs 22.4 GB fetched
+    // per frame (profiles/r04/r4g), for 11% more slots.  A scene whose records
+    // stay in L2 gains nothing from it, and its kernels then skip the pad-bit
+    // arithmetic (kFeatPad off: config 3 0.303-0.304 vs 0.306-0.307 ms,
+    // profiles/r04/r4m).
+    int  leaf_align = 2;
+    int  accel_half = 0;           // at the next upload: accel records in format 1, the internal boxes in
+                                   //   half precision (accel_build.h)
+    int  accel_wide = 0;           // at the next upload: the 4-wide tree, format 2 (overrides accel_half)
+    int  split_bounce = 0;         // accel walk: paths alive at this bounce finish in a second kernel
                                    //   (0 = one kernel)
-    int  accel = RT_ACCEL;         // at the next upload: 0 = the reference's tree and order; 1 / 8 = the
-                                   //   SAH tree in 1 / 8 (octant) layouts (accel_build.h)
+    // At the next upload: 0 = the reference's tree and order; 1 / 8 = the
+    // binned-SAH tree in 1 / 8 (octant) layouts (accel_build.h).
+    // Config 3 0.1279-0.1288 ms per frame against 0.2962-0.2964 for the
+    // reference's tree and order, config 5 1.24-1.25 against 7.84 ms, config 6
+    // 0.140 against 0.342 (profiles/r05/r5a, r5b); 1 layout: 0.1365, 1.40, 0.148.
+    int  accel = 8;
     int  order_split = 0;          // heavy_first: only tiles costing >= this percent of the costliest go first
                                    //   (in cost order); the rest keep their raster order (0 = all by cost)
     int  order_frames = 0;         // heavy_first, several frames per launch: the non-leading tiles row by row
@@ -2090,6 +2073,67 @@ int rt_render_poll(rt_ctx* ctx, uint64_t ticket, int* done) {
     return RT_OK;
 }
 
+// The settable options, each declared once: its name, its field of rt_ctx, and
+// the values rt_set_option takes for it: any in [lo, hi] (in_range), or one
+// of set[0..n) (one_of: its range is empty).  rt_get_option reads the same
+// field.
+struct Option {
+    const char*  name;
+    int rt_ctx::* field;
+    int64_t      lo, hi;
+    int          n;
+    int64_t      set[3];
+};
+static constexpr Option in_range(const char* name, int rt_ctx::* field, int64_t lo, int64_t hi) {
+    return {name, field, lo, hi, 0, {}};
+}
+static constexpr Option one_of(const char* name, int rt_ctx::* field, int64_t a, int64_t b) {
+    return {name, field, 0, -1, 2, {a, b}};
+}
+static constexpr Option one_of(const char* name, int rt_ctx::* field, int64_t a, int64_t b, int64_t c) {
+    return {name, field, 0, -1, 3, {a, b, c}};
+}
+static const Option kOptions[] = {
+    in_range("coop_lanes", &rt_ctx::coop_lanes, -1, 64),
+    in_range("extensions", &rt_ctx::ext, 0, 15),
+    one_of("walk", &rt_ctx::walk, 0, 2),
+    one_of("coop_window", &rt_ctx::coop_window, 0, 32, 64),
+    one_of("coop_walk", &rt_ctx::coop_walk, 0, 1),
+    one_of("block_waves", &rt_ctx::block_waves, 1, 4),
+    one_of("heavy_first", &rt_ctx::heavy_first, 0, 1),
+    in_range("heavy_tiles", &rt_ctx::heavy_tiles, -1, 1 << 20),
+    in_range("heavy_factor", &rt_ctx::heavy_factor, 10, 100000),
+    one_of("heavy_pixels", &rt_ctx::heavy_pixels, 0, 1),
+    in_range("heavy_pixel_factor", &rt_ctx::heavy_pixel_factor, 1, 100000),
+    one_of("reuse_order", &rt_ctx::reuse_order, 0, 1),
+    in_range("heavy_cap", &rt_ctx::heavy_cap, 1, 100),
+    in_range("async_slots", &rt_ctx::async_slots, 1, kMaxSlots),
+    one_of("copy_streams", &rt_ctx::copy_streams, 1, 2),
+    in_range("concurrent_launches", &rt_ctx::concurrent_launches, 1, 64),
+    one_of("learn_cost", &rt_ctx::learn_cost, 0, 1),
+    one_of("order_frames", &rt_ctx::order_frames, 0, 1),
+    in_range("order_split", &rt_ctx::order_split, 0, 100),
+    one_of("learn_alone", &rt_ctx::learn_alone, 0, 1),
+    in_range("xcd_order", &rt_ctx::xcd_order, 0, 4096),
+    in_range("accel_octants", &rt_ctx::accel_octants, 0, 7),
+    one_of("learn_device", &rt_ctx::learn_device, 0, 1),
+    in_range("leaf_align", &rt_ctx::leaf_align, 0, 2),      // these four take effect at the next
+    one_of("accel", &rt_ctx::accel, 0, 1, 8),               //   rt_upload_scene
+    one_of("accel_half", &rt_ctx::accel_half, 0, 1),
+    one_of("accel_wide", &rt_ctx::accel_wide, 0, 1),
+    in_range("split_bounce", &rt_ctx::split_bounce, 0, 64),
+    in_range("heavy_stream", &rt_ctx::heavy_stream, 0, 2),
+    one_of("graph", &rt_ctx::graph, 0, 1),
+    one_of("diag", &rt_ctx::diag, 0, 1),
+    in_range("wave_tile", &rt_ctx::wave_tile, -1, 3),
+};
+
+static const Option* find_option(const char* name) {
+    for (const Option& o : kOptions)
+        if (std::strcmp(name, o.name) == 0) return &o;
+    return nullptr;
+}
+
 int rt_set_option(rt_ctx* ctx, const char* name, int64_t value) {
     if (!ctx || !name) { set_error("rt_set_option: null argument"); return RT_ERR_INVALID_ARG; }
     static const char* const archived[] = {"shade_min", "blocks_per_cu", "seg_limit", "heavy_budget", "prio_after"};
@@ -2098,130 +2142,45 @@ int rt_set_option(rt_ctx* ctx, const char* name, int64_t value) {
             set_error("rt_set_option: %s belonged to a schedule archived in round 3 (profiles/r03/archive)", name);
             return RT_ERR_INVALID_ARG;
         }
-    if (std::strcmp(name, "kernel") == 0 && value == 0) {
-        // the one kernel (kernels 1-3, persistent / split / tiered, are archived)
-    } else if (std::strcmp(name, "coop_lanes") == 0 && value >= -1 && value <= 64) {
-        ctx->coop_lanes = (int)value;
-    } else if (std::strcmp(name, "extensions") == 0 && value >= 0 && value <= 15) {
-        ctx->ext = (int)value;
-    } else if (std::strcmp(name, "walk") == 0 && (value == 0 || value == 2)) {
-        ctx->walk = (int)value;
-    } else if (std::strcmp(name, "coop_window") == 0 && (value == 0 || value == 32 || value == 64)) {
-        ctx->coop_window = (int)value;
-    } else if (std::strcmp(name, "coop_walk") == 0 && (value == 0 || value == 1)) {
-        ctx->coop_walk = (int)value;
-    } else if (std::strcmp(name, "block_waves") == 0 && (value == 1 || value == 4)) {
-        ctx->block_waves = (int)value;
-    } else if (std::strcmp(name, "heavy_first") == 0 && (value == 0 || value == 1)) {
-        ctx->heavy_first = (int)value;
-    } else if (std::strcmp(name, "heavy_tiles") == 0 && value >= -1 && value <= (1 << 20)) {
-        ctx->heavy_tiles = (int)value;
-    } else if (std::strcmp(name, "heavy_factor") == 0 && value >= 10 && value <= 100000) {
-        ctx->heavy_factor = (int)value;
-    } else if (std::strcmp(name, "heavy_pixels") == 0 && (value == 0 || value == 1)) {
-        ctx->heavy_pixels = (int)value;
-    } else if (std::strcmp(name, "heavy_pixel_factor") == 0 && value >= 1 && value <= 100000) {
-        ctx->heavy_pixel_factor = (int)value;
-    } else if (std::strcmp(name, "reuse_order") == 0 && (value == 0 || value == 1)) {
-        ctx->reuse_order = (int)value;
-    } else if (std::strcmp(name, "heavy_cap") == 0 && value >= 1 && value <= 100) {
-        ctx->heavy_cap = (int)value;
-    } else if (std::strcmp(name, "async_slots") == 0 && value >= 1 && value <= kMaxSlots) {
-        ctx->async_slots = (int)value;
-    } else if (std::strcmp(name, "copy_streams") == 0 && (value == 1 || value == 2)) {
-        ctx->copy_streams = (int)value;
-    } else if (std::strcmp(name, "concurrent_launches") == 0 && value >= 1 && value <= 64) {
-        ctx->concurrent_launches = (int)value;
-    } else if (std::strcmp(name, "learn_cost") == 0 && (value == 0 || value == 1)) {
-        ctx->learn_cost = (int)value;
-    } else if (std::strcmp(name, "order_frames") == 0 && (value == 0 || value == 1)) {
-        ctx->order_frames = (int)value;
-    } else if (std::strcmp(name, "order_split") == 0 && value >= 0 && value <= 100) {
-        ctx->order_split = (int)value;
-    } else if (std::strcmp(name, "learn_alone") == 0 && (value == 0 || value == 1)) {
-        ctx->learn_alone = (int)value;
-    } else if (std::strcmp(name, "xcd_order") == 0 && value >= 0 && value <= 4096) {
-        ctx->xcd_order = (int)value;
-    } else if (std::strcmp(name, "accel_octants") == 0 && value >= 0 && value <= 7) {
-        ctx->accel_octants = (int)value;
-    } else if (std::strcmp(name, "learn_device") == 0 && (value == 0 || value == 1)) {
-        ctx->learn_device = (int)value;
-    } else if (std::strcmp(name, "leaf_align") == 0 && value >= 0 && value <= 2) {
-        ctx->leaf_align = (int)value;                   // takes effect at the next rt_upload_scene
-    } else if (std::strcmp(name, "accel") == 0 && (value == 0 || value == 1 || value == 8)) {
-        ctx->accel = (int)value;                        // takes effect at the next rt_upload_scene
-    } else if (std::strcmp(name, "split_bounce") == 0 && value >= 0 && value <= 64) {
-        ctx->split_bounce = (int)value;
-    } else if (std::strcmp(name, "accel_half") == 0 && (value == 0 || value == 1)) {
-        ctx->accel_half = (int)value;                   // takes effect at the next rt_upload_scene
-    } else if (std::strcmp(name, "accel_wide") == 0 && (value == 0 || value == 1)) {
-        ctx->accel_wide = (int)value;                   // takes effect at the next rt_upload_scene
-    } else if (std::strcmp(name, "heavy_stream") == 0 && value >= 0 && value <= 2) {
-        ctx->heavy_stream = (int)value;
-    } else if (std::strcmp(name, "graph") == 0 && (value == 0 || value == 1)) {
-        ctx->graph = (int)value;
-    } else if (std::strcmp(name, "diag") == 0 && (value == 0 || value == 1)) {
-        ctx->diag = (int)value;
-    } else if (std::strcmp(name, "wave_tile") == 0 && value >= -1 && value <= 3) {
-        ctx->wave_tile = (int)value;
-    } else {
-        set_error("rt_set_option: unknown option or bad value: %s = %lld", name, (long long)value);
-        return RT_ERR_INVALID_ARG;
+    // the one kernel (kernels 1-3, persistent / split / tiered, are archived)
+    if (std::strcmp(name, "kernel") == 0 && value == 0) return RT_OK;
+    if (const Option* o = find_option(name)) {
+        bool ok = value >= o->lo && value <= o->hi;
+        for (int k = 0; k < o->n; ++k) ok = ok || value == o->set[k];
+        if (ok) {
+            ctx->*(o->field) = (int)value;
+            return RT_OK;
+        }
     }
-    return RT_OK;
+    set_error("rt_set_option: unknown option or bad value: %s = %lld", name, (long long)value);
+    return RT_ERR_INVALID_ARG;
 }
 
 int rt_get_option(rt_ctx* ctx, const char* name, int64_t* value) {
     if (!ctx || !name || !value) { set_error("rt_get_option: null argument"); return RT_ERR_INVALID_ARG; }
-    if (std::strcmp(name, "kernel") == 0) *value = 0;
-    else if (std::strcmp(name, "wave_tile") == 0) *value = ctx->wave_tile;
-    else if (std::strcmp(name, "wave_tile_used") == 0)
-        *value = ctx->dev.empty() ? 0 : wave_tile_of(ctx, ctx->dev[0]);
-    else if (std::strcmp(name, "coop_lanes") == 0) *value = ctx->coop_lanes;
-    else if (std::strcmp(name, "walk") == 0) *value = ctx->walk;
-    else if (std::strcmp(name, "coop_walk") == 0) *value = ctx->coop_walk;
-    else if (std::strcmp(name, "coop_window") == 0) *value = ctx->coop_window;
-    else if (std::strcmp(name, "coop_window_used") == 0)
-        *value = ctx->dev.empty() ? 0 : coop_window_of(ctx, ctx->dev[0]);
-    else if (std::strcmp(name, "block_waves") == 0) *value = ctx->block_waves;
-    else if (std::strcmp(name, "heavy_first") == 0) *value = ctx->heavy_first;
-    else if (std::strcmp(name, "heavy_tiles") == 0) *value = ctx->heavy_tiles;
-    else if (std::strcmp(name, "heavy_stream") == 0) *value = ctx->heavy_stream;
-    else if (std::strcmp(name, "graph") == 0) *value = ctx->graph;
-    else if (std::strcmp(name, "learn_cost") == 0) *value = ctx->learn_cost;
-    else if (std::strcmp(name, "order_split") == 0) *value = ctx->order_split;
-    else if (std::strcmp(name, "learn_alone") == 0) *value = ctx->learn_alone;
-    else if (std::strcmp(name, "xcd_order") == 0) *value = ctx->xcd_order;
-    else if (std::strcmp(name, "accel_octants") == 0) *value = ctx->accel_octants;
-    else if (std::strcmp(name, "learn_device") == 0) *value = ctx->learn_device;
-    else if (std::strcmp(name, "leaf_align") == 0) *value = ctx->leaf_align;
-    else if (std::strcmp(name, "accel") == 0) *value = ctx->accel;
-    else if (std::strcmp(name, "accel_half") == 0) *value = ctx->accel_half;
-    else if (std::strcmp(name, "split_bounce") == 0) *value = ctx->split_bounce;
-    else if (std::strcmp(name, "accel_half_used") == 0) *value = ctx->dev.empty() ? 0 : ctx->dev[0].scene.half;
-    else if (std::strcmp(name, "accel_wide") == 0) *value = ctx->accel_wide;
-    else if (std::strcmp(name, "accel_wide_used") == 0) *value = ctx->dev.empty() ? 0 : ctx->dev[0].scene.wide;
-    else if (std::strcmp(name, "walk_bytes") == 0) *value = ctx->dev.empty() ? 0 : (int64_t)walk_bytes(ctx->dev[0]);
-    else if (std::strcmp(name, "accel_used") == 0) *value = ctx->dev.empty() ? 0 : ctx->dev[0].scene.n_layouts;
-    else if (std::strcmp(name, "leaf_align_used") == 0) *value = ctx->dev.empty() ? 0 : ctx->dev[0].scene.padded;
-    else if (std::strcmp(name, "heavy_factor") == 0) *value = ctx->heavy_factor;
-    else if (std::strcmp(name, "concurrent_launches") == 0) *value = ctx->concurrent_launches;
-    else if (std::strcmp(name, "async_slots") == 0) *value = ctx->async_slots;
-    else if (std::strcmp(name, "copy_streams") == 0) *value = ctx->copy_streams;
-    else if (std::strcmp(name, "heavy_cap") == 0) *value = ctx->heavy_cap;
-    else if (std::strcmp(name, "reuse_order") == 0) *value = ctx->reuse_order;
-    else if (std::strcmp(name, "heavy_pixels") == 0) *value = ctx->heavy_pixels;
-    else if (std::strcmp(name, "heavy_pixel_factor") == 0) *value = ctx->heavy_pixel_factor;
-    else if (std::strcmp(name, "heavy_pixels_used") == 0) *value = ctx->dev.empty() ? 0 : ctx->dev[0].last_heavy_px;
-    else if (std::strcmp(name, "heavy_tiles_used") == 0) *value = ctx->dev.empty() ? 0 : ctx->dev[0].last_heavy;
-    else if (std::strcmp(name, "plain_kernels") == 0) *value = ctx->dev.empty() ? 0 : (int64_t)ctx->dev[0].plain_kernels;
-    else if (std::strcmp(name, "extensions") == 0) *value = ctx->ext;
-    else if (std::strcmp(name, "hw_queues") == 0) *value = ctx->hw_queues;
-    else if (std::strcmp(name, "order_frames") == 0) *value = ctx->order_frames;
+    if (const Option* o = find_option(name)) {
+        *value = ctx->*(o->field);
+        return RT_OK;
+    }
+    // the read-only names: what the last upload or launch chose (device 0's)
+    const auto is = [name](const char* s) { return std::strcmp(name, s) == 0; };
+    PerDevice* p = ctx->dev.empty() ? nullptr : &ctx->dev[0];
+    if (is("kernel")) *value = 0;
+    else if (is("wave_tile_used")) *value = p ? wave_tile_of(ctx, *p) : 0;
+    else if (is("coop_window_used")) *value = p ? coop_window_of(ctx, *p) : 0;
+    else if (is("accel_half_used")) *value = p ? p->scene.half : 0;
+    else if (is("accel_wide_used")) *value = p ? p->scene.wide : 0;
+    else if (is("accel_used")) *value = p ? p->scene.n_layouts : 0;
+    else if (is("walk_bytes")) *value = p ? (int64_t)walk_bytes(*p) : 0;
+    else if (is("leaf_align_used")) *value = p ? p->scene.padded : 0;
+    else if (is("heavy_pixels_used")) *value = p ? p->last_heavy_px : 0;
+    else if (is("heavy_tiles_used")) *value = p ? p->last_heavy : 0;
+    else if (is("plain_kernels")) *value = p ? (int64_t)p->plain_kernels : 0;
+    else if (is("hw_queues")) *value = ctx->hw_queues;
     // 1 when rt_render_async's slots cannot each have a hardware queue of their
     // own (async_slots + 2 > hw_queues: the slots' traces then share queues and
     // run one after another); start the host with GPU_MAX_HW_QUEUES >= slots + 2
-    else if (std::strcmp(name, "queues_short") == 0) *value = ctx->async_slots + 2 > ctx->hw_queues ? 1 : 0;
+    else if (is("queues_short")) *value = ctx->async_slots + 2 > ctx->hw_queues ? 1 : 0;
     else { set_error("rt_get_option: unknown option %s", name); return RT_ERR_INVALID_ARG; }
     return RT_OK;
 }

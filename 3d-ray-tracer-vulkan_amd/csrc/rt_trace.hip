@@ -384,32 +384,17 @@ constexpr uint32_t kIdx = 0x1FFFFFFFu;       // node index bits of a link word (
 constexpr uint32_t kTri = 0x1FFFFFFFu;       // triangle index bits of a leaf's link word (bit 29: pad after
                                              //   it on the reference's tree, kForce on option accel's)
 __device__ __forceinline__ bool accel_enter(float te, float closest) { return te <= closest * kRelax + kRelaxAbs; }
-// (A/B builds: RT_THIN_MARGIN 0 = round 5's rule, the 2^-10 margin
-// everywhere, not exact for thin triangles: make variant NAME=x
-// FLAGS=-DRT_THIN_MARGIN=0)
-#ifndef RT_THIN_MARGIN
-#define RT_THIN_MARGIN 1
-#endif
-// Format 0's entry rule for a record with link word aw.
+// Format 0's entry rule for a record with link word aw.  (Round 5's rule, the
+// 2^-10 margin everywhere, is not exact for thin triangles: DESIGN.md §5.)
 __device__ __forceinline__ bool accel_enter_w(float te, float closest, uint32_t aw) {
-#if RT_THIN_MARGIN
     return accel_enter(te, closest) || (aw & kForce) != 0u;
-#else
-    (void)aw;
-    return accel_enter(te, closest);
-#endif
 }
 // The same with the bound closest_t * (1 + 2^-10) + 2^-10 (the same two
 // roundings) kept in lim, recomputed only when closest_t changes: the per-node
 // walk's form (two VALU instructions fewer per step).
 __device__ __forceinline__ float accel_lim(float closest) { return closest * kRelax + kRelaxAbs; }
 __device__ __forceinline__ bool accel_enter_lim(float te, float lim, uint32_t aw) {
-#if RT_THIN_MARGIN
     return te <= lim || (aw & kForce) != 0u;
-#else
-    (void)aw;
-    return te <= lim;
-#endif
 }
 __device__ __forceinline__ bool accel_enter_r(float te, float closest, float r) {
     return te <= closest * r + kRelaxAbs;
@@ -419,27 +404,14 @@ __device__ __forceinline__ bool accel_take(float t, int tri, float closest, int 
 }
 
 // ------------------------------------------------------------ cooperative walk --
-#ifndef RT_CHAIN
-// The lockstep walk's next records: 2 = buffer loads whose address is one
-// shift of the slot index (config 3 0.2947-0.2960 vs 0.2965-0.2980 ms, config 5
-// 8.07-8.10 vs 8.10-8.11, profiles/r04/r4s abchain; records < 4 GB, checked at
-// upload); 3 = the same with two selects (equal: 0.2957-0.2963 vs
-// 0.2955-0.2977, profiles/r04/r4v); 1 = one select on the chain with global
-// loads (slower: 0.298-0.300, 8.42-8.56); 0 = global loads.
-#define RT_CHAIN 2
-#endif
-#ifndef RT_COOP_BUF
-// 1 = cooperative windows through buffer loads: slower (config 3 0.2969-0.2986 vs
-// 0.2946-0.2957 ms; 8 B more scratch per lane; profiles/r04/r4y), so 0
-#define RT_COOP_BUF 0
-#endif
-#if RT_COOP_BUF
-__device__ __forceinline__ float4 wbuf_s(__amdgpu_buffer_rsrc_t r, int voff, unsigned soff) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, (int)soff, 0);
-    return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-}
-#endif
-#if RT_CHAIN >= 2
+// The lockstep walk's next records come by buffer loads whose address is one
+// shift of the slot index (config 3 0.2947-0.2960 vs 0.2965-0.2980 ms with
+// global loads, config 5 8.07-8.10 vs 8.10-8.11, profiles/r04/r4s abchain;
+// records < 4 GB, checked at upload).  A second select on the chain measured
+// equal (profiles/r04/r4v), one select with global loads slower (r4s).
+// Cooperative windows through buffer loads measured slower (profiles/r04/r4y),
+// and so did scalar-cache loads for steps whose lanes agree:
+// the windows use plain loads.
 __device__ __forceinline__ float4 wbuf(__amdgpu_buffer_rsrc_t r, int slot, int off) {
     const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)((unsigned)slot << 5) + off, 0, 0);
     return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
@@ -448,20 +420,6 @@ __device__ __forceinline__ float4 wbuf(__amdgpu_buffer_rsrc_t r, int slot, int o
 __device__ __forceinline__ float4 wbuf_b(__amdgpu_buffer_rsrc_t r, unsigned byte, int off) {
     const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte + off, 0, 0);
     return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-}
-#endif
-#ifndef RT_ACC_SCALAR
-// 1 = a walk step whose walking lanes all go to one slot loads it through the
-// scalar cache (one s_load per 16 B, no vector-memory issue); A/B builds
-#define RT_ACC_SCALAR 0
-#endif
-// 16-B piece k of the walk records through the scalar cache: k must be
-// wave-uniform (readfirstlane), the records read-only for the kernel's life.
-__device__ __forceinline__ float4 sbuf(const float4* base, int k) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(4))) const v4f cv4f;
-    const v4f v = reinterpret_cast<cv4f*>(reinterpret_cast<uintptr_t>(base))[k];
-    return make_float4(v[0], v[1], v[2], v[3]);
 }
 // A half-format accel record's 16-B slot (accel_build.h format 1).
 __device__ __forceinline__ float4 hbuf(__amdgpu_buffer_rsrc_t r, int slot) {
@@ -475,9 +433,6 @@ __device__ __forceinline__ float half_lo(uint32_t w) {
 __device__ __forceinline__ float half_hi(uint32_t w) {
     return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16));
 }
-#ifndef RT_COOP_DPP
-#define RT_COOP_DPP 1      // a leaf's triangle from the next lane by DPP (0: loaded by the lane, A/B builds)
-#endif
 //
 // The whole wave walks ONE ray (arguments wave-uniform), replaying the
 // reference's visit sequence exactly:
@@ -511,14 +466,6 @@ __device__ __forceinline__ int coop_walk(const float4* __restrict__ walk, int en
                                          unsigned long long& c_tri, bool& incons) {
     const int lane = threadIdx.x & 63;
     int windows = 0;
-#if RT_COOP_BUF
-    // buffer loads: lane k's offset k x 32 B is fixed, the window start is the
-    // scalar offset, so no vector instruction sits between the replay's next n
-    // and the window's loads
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float4*>(walk), 0, (int)((unsigned)(end + 2) * 32u), 0x00020000);
-    const int voff = lane << 5;
-#endif
     while (n < end) {
         ++windows;
         const int j = n + lane;
@@ -528,28 +475,11 @@ __device__ __forceinline__ int coop_walk(const float4* __restrict__ walk, int en
         int sk = 0, tri = -1;
         bool ind = false, tv = false, lf = false, pd = false;
         float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A;
-#if RT_COOP_DPP
-#if RT_COOP_BUF
-        if (ld) {                                                   // window start in the scalar offset
-            A = wbuf_s(rs, voff, (unsigned)n << 5);
-            B = wbuf_s(rs, voff + 16, (unsigned)n << 5);
-        }
-#else
         if (ld) {
             A = walk[2 * j];
             B = walk[2 * j + 1];
         }
-#endif
         const float4 Q0 = next_lane(A), Q1 = next_lane(B);          // the slot after this one (every lane active)
-#else
-        float4 Q0 = A, Q1 = A;                                       // (A/B variant: the slot after, loaded)
-        if (ld) {
-            A = walk[2 * j];
-            B = walk[2 * j + 1];
-            Q0 = walk[2 * j + 2];
-            Q1 = walk[2 * j + 3];
-        }
-#endif
         if (ld) {
             slab(A, B, o, inv, te, ind);
             const uint32_t aw = __float_as_uint(A.w);
@@ -566,7 +496,7 @@ __device__ __forceinline__ int coop_walk(const float4* __restrict__ walk, int en
             }
             tri = (int)(aw & kTri);
             if (ACC) law = aw;
-            if (lf && ind && (ACC ? accel_enter_w(te, closest, aw) : te < closest) && (!RT_COOP_DPP || lane < WIN - 1))
+            if (lf && ind && (ACC ? accel_enter_w(te, closest, aw) : te < closest) && lane < WIN - 1)
                 tv = tri_test(make_float4(B.w, Q0.x, Q0.y, 0.f), make_float4(Q0.z, Q0.w, Q1.x, 0.f),
                               make_float4(Q1.y, Q1.z, Q1.w, 0.f), o, d, tt);
         }
@@ -575,7 +505,7 @@ __device__ __forceinline__ int coop_walk(const float4* __restrict__ walk, int en
         const uint64_t Lf = __ballot(lf);
         const uint64_t Pd = PAD ? __ballot(pd) : 0ull;              // a pad slot follows (leaf alignment)
         int lim = min(WIN, end - n);
-        if (RT_COOP_DPP && lim == WIN && ((Lf >> (WIN - 1)) & 1ull))
+        if (lim == WIN && ((Lf >> (WIN - 1)) & 1ull))
             lim = WIN - 1;                                   // its triangle is past the window
         int k = 0;
         while (k < lim) {
@@ -1030,35 +960,21 @@ __device__ __forceinline__ void heavy_pixel(const TraceArgs& a, int f, int lx, i
 // waves (64 VGPRs, ~20 B per lane of per-segment spills) beat 7 on config 3
 // (0.298-0.299 vs 0.301-0.302 ms) and config 6 (0.343-0.344 vs 0.364-0.365),
 // config 5 even (profiles/r02/occupancy/wpe8).  The frontier (heavy-tile)
-// instantiations keep their registers.
-#ifndef RT_SIMPLE_WPE
-#define RT_SIMPLE_WPE 8
-#endif
-// option accel's kernels (A/B builds: make variant FLAGS=-DRT_ACCEL_WPE=7)
-#ifndef RT_ACCEL_WPE
-#define RT_ACCEL_WPE RT_SIMPLE_WPE
-#endif
-// 1 = an accel leaf's triangle is loaded only once its box is hit (a second
-// dependent round trip for the quarter of leaf visits that test it, two loads
-// fewer for the rest); 0 = with the leaf's box, as the reference-order walk
-#ifndef RT_ACC_LAZY
-#define RT_ACC_LAZY 0
-#endif
+// instantiations keep their registers.  Option accel's kernels take the same
+// floor.
+constexpr int kWavesPerEu = 8;
 // s_setprio level of a wave while it walks: the walk's dependent chain
 // (record, slab test, next address, next load) issues ahead of the waves that
 // shade, whose VALU work is not on any load's path.  1, 2 and 3 measured alike,
 // 1.0-1.5% per frame on configs 3 and 5 against 0 (profiles/r06/r6ab, r6ac).
-#ifndef RT_WALK_PRIO
-#define RT_WALK_PRIO 2
-#endif
-// 1 = option accel's format-0 walk starts inside the root (DevScene::root_enter;
-// A/B builds: 0 = the root's slab test first, as the model's orc_accel_root(0))
-#ifndef RT_ROOT_ENTER
-#define RT_ROOT_ENTER 1
-#endif
+constexpr int kWalkPrio = 2;
+// An accel leaf's triangle is loaded with the leaf's box, as on the
+// reference-order walk: loading it only once the box is hit measured slower
+// (profiles/r06/r6z).  Option accel's format-0 walk starts inside the root
+// (DevScene::root_enter; profiles/r06/r6s).
 template <bool COUNT, bool DIAG = false, int FEAT = 0, int WALK = 2>
 __global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu((FEAT & kFeatFrontier) ? 1 : (FEAT & kFeatAccel) ? RT_ACCEL_WPE : RT_SIMPLE_WPE)))
+__attribute__((amdgpu_waves_per_eu((FEAT & kFeatFrontier) ? 1 : kWavesPerEu)))
 void trace_simple(TraceArgs a) {
     // Pad bits (leaf_align): the production kernels (cooperative tail, no
     // extensions or frontier tail) read them only when built with kFeatPad, so
@@ -1255,7 +1171,7 @@ void trace_simple(TraceArgs a) {
         // which fail it too (their boxes lie inside), so results are the
         // same, and every segment saves the root's step; the root's two
         // children count as visited, as when the root is entered.
-        if (ACC && !HALF && !WIDE && RT_ROOT_ENTER && a.scene.root_enter) {
+        if (ACC && !HALF && !WIDE && a.scene.root_enter) {
             n += 1;
             nleaf = ((a.scene.root_first_leaf >> oct) & 1) != 0;
             if (COUNT && alive) c_node += 2;
@@ -1280,8 +1196,7 @@ void trace_simple(TraceArgs a) {
             float4 A, B, Q0, Q1;
             const float4* __restrict__ wr = a.scene.walk;
             // a buffer resource over the records: the next slot's address is one
-            // shift of its index (the offset field adds the 16-B halves); the
-            // half-format walk uses it whatever RT_CHAIN is
+            // shift of its index (the offset field adds the 16-B halves)
             const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<float4*>(wr), 0,
                 WIDE ? (int)((unsigned)(a.scene.end2 + 1) * 64u)
@@ -1305,16 +1220,15 @@ void trace_simple(TraceArgs a) {
                 }
             }
             float lim = accel_lim(closest);                          // ACC: closest_t's entry bound
-            // the walk's dependent chain issues ahead of waves shading (RT_WALK_PRIO)
-            if (RT_WALK_PRIO) __builtin_amdgcn_s_setprio(RT_WALK_PRIO);
+            // the walk's dependent chain issues ahead of waves shading
+            __builtin_amdgcn_s_setprio(kWalkPrio);
             // Option accel's format-0 walk tracks its record as a byte offset
             // (slot << 5; the records stay below 2^27 slots, so it and the
             // layout's end fit 32 bits): the next record's address is one
             // select of two values known before the slab test ends, the
             // skip's being its link word << 5 (the shift drops kForce and the
             // L bit), and the slot index is recovered after the loop.
-            constexpr bool BYTES = ACC && !HALF && !WIDE && !PAD && WALK == 2 && RT_CHAIN == 2 &&
-                                   !RT_ACC_SCALAR && !RT_ACC_LAZY;
+            constexpr bool BYTES = ACC && !HALF && !WIDE && !PAD && WALK == 2;
             unsigned nb = (unsigned)n << 5;
             const unsigned lend_b = (unsigned)lend << 5;
             while (walking) {
@@ -1385,19 +1299,13 @@ void trace_simple(TraceArgs a) {
                         const int m_hit = -(int)hb, m_leaf = -(int)nleaf;
                         const int n_int = (n_hit & m_hit) | ((int)(aw & kIdx) & ~m_hit);
                         nxt = (n_leaf & m_leaf) | (n_int & ~m_leaf);
+                    } else if (BYTES) {
+                        const unsigned tb = nb + (nleaf ? 64u : 32u);        // known before the slab test ends
+                        nb = (hb || nleaf) ? tb : (aw << 5);
+                        nxt = 0;                                             // (the slot: nb >> 5)
                     } else {
-#if RT_CHAIN == 1 || RT_CHAIN == 2
-                        if (BYTES) {
-                            const unsigned tb = nb + (nleaf ? 64u : 32u);    // known before the slab test ends
-                            nb = (hb || nleaf) ? tb : (aw << 5);
-                            nxt = 0;                                         // (the slot: nb >> 5)
-                        } else {
-                            const int t = n + 1 + (int)nleaf;                // known before the slab test ends
-                            nxt = (hb || nleaf) ? t : (int)(aw & kIdx);
-                        }
-#else
-                        nxt = nleaf ? n + 2 : (hb ? n + 1 : (int)(aw & kIdx));
-#endif
+                        const int t = n + 1 + (int)nleaf;                    // known before the slab test ends
+                        nxt = (hb || nleaf) ? t : (int)(aw & kIdx);
                     }
                     // accel records: L(first) is bit 31 of word 7, L(skip) / L(next) bit 31
                     // of word 3 (two sign tests); the reference's: bit 0 of word 7
@@ -1405,18 +1313,6 @@ void trace_simple(TraceArgs a) {
                                         : ((((hb && !nleaf) ? bw : (aw >> 31)) & 1u) != 0u);
                     const float v0x = B.w;                                   // a leaf's v0.x
                     if (COUNT && hb && !nleaf) c_node += 2;
-#if RT_ACC_SCALAR
-                    // one slot for every walking lane: the scalar cache
-                    const int nf = __builtin_amdgcn_readfirstlane(nxt);
-                    const bool uni = ACC && !PAD && __ballot(nxt != nf) == 0;
-                    if (uni) {
-                        A = sbuf(wr, 2 * nf);
-                        B = sbuf(wr, 2 * nf + 1);
-                    } else {
-                        A = wbuf(wrs, nxt, 0);                               // slot end is padding
-                        B = wbuf(wrs, nxt, 16);
-                    }
-#elif RT_CHAIN >= 2
                     if (BYTES) {
                         A = wbuf_b(wrs, nb, 0);                              // slot end is padding
                         B = wbuf_b(wrs, nb, 16);
@@ -1424,25 +1320,8 @@ void trace_simple(TraceArgs a) {
                         A = wbuf(wrs, nxt, 0);                               // slot end is padding
                         B = wbuf(wrs, nxt, 16);
                     }
-#elif RT_CHAIN == 1
-                    {
-                        const float4* p = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(wr) +
-                                                                          ((size_t)(unsigned)nxt << 5));
-                        A = p[0];                                            // slot end is padding
-                        B = p[1];
-                    }
-#else
-                    A = wr[2 * nxt];                                         // slot end is padding
-                    B = wr[2 * nxt + 1];
-#endif
                     if (hb && nleaf) {                                       // hit_triangle (:196-200)
                         if (COUNT) ++c_tri;
-#if RT_CHAIN >= 2
-                        if (ACC && RT_ACC_LAZY) {
-                            Q0 = wbuf(wrs, n, 32);
-                            Q1 = wbuf(wrs, n, 48);
-                        }
-#endif
                         float t;
                         if (tri_test(make_float4(v0x, Q0.x, Q0.y, 0.f), make_float4(Q0.z, Q0.w, Q1.x, 0.f),
                                      make_float4(Q1.y, Q1.z, Q1.w, 0.f), o, d, t) &&
@@ -1456,16 +1335,7 @@ void trace_simple(TraceArgs a) {
                         }
                     }
                     const bool inb = BYTES ? nb < lend_b : nxt < (ACC ? lend : wend);
-                    if (nl && inb && !(ACC && RT_ACC_LAZY)) {
-#if RT_ACC_SCALAR
-                        if (uni) {
-                            Q0 = sbuf(wr, 2 * nf + 2);
-                            Q1 = sbuf(wr, 2 * nf + 3);
-                        } else {
-                            Q0 = wbuf(wrs, nxt, 32);
-                            Q1 = wbuf(wrs, nxt, 48);
-                        }
-#elif RT_CHAIN >= 2
+                    if (nl && inb) {
                         if (BYTES) {
                             Q0 = wbuf_b(wrs, nb, 32);
                             Q1 = wbuf_b(wrs, nb, 48);
@@ -1473,10 +1343,6 @@ void trace_simple(TraceArgs a) {
                             Q0 = wbuf(wrs, nxt, 32);
                             Q1 = wbuf(wrs, nxt, 48);
                         }
-#else
-                        Q0 = wr[2 * nxt + 2];
-                        Q1 = wr[2 * nxt + 3];
-#endif
                     }
                     if (!BYTES) n = nxt;
                     nleaf = nl;
@@ -1486,7 +1352,7 @@ void trace_simple(TraceArgs a) {
                 if ((FEAT & kFeatCoopTail) && __popcll(__ballot(walking)) <= coop_lanes) break;
             }
             if (BYTES) n = (int)(nb >> 5);
-            if (RT_WALK_PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
         }
         if (FEAT & kFeatCoopTail) {
             // Every lane is here.  Finish the remaining walks one ray at a

@@ -479,7 +479,8 @@ int rt_render_poll(rt_ctx* ctx, uint64_t ticket, int* done);
  * RTAMD_HEAVY_TILES, RTAMD_HEAVY_FACTOR, RTAMD_HEAVY_STREAM (0 / 1 / 2),
  * RTAMD_HEAVY_PIXELS, RTAMD_LEARN_COST and RTAMD_GRAPH. */
 int rt_set_option(rt_ctx* ctx, const char* name, int64_t value);
-/* Diagnostics: with option "diag" = 1, the kernel records per wave
+/* Diagnostics: with option "diag" = 1 (0 or 1, default 0; rt_get_option reads
+ * it back like every settable option), the kernel records per wave
  * 8 words: {start, end} (s_memrealtime, 100 MHz), {XCC id << 32 | HW_ID},
  * {block << 8 | wave}, {lockstep walk iterations}, {cooperative windows},
  * {ticks spent in the cooperative tail}, {the lanes' own lockstep steps,

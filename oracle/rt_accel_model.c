@@ -55,8 +55,8 @@ int orc_accel_octants(int mask) {
     return 0;
 }
 
-/* Format 0's root entry (1, the kernel's default: its slab test skipped; 0:
- * tested first, as an RT_ROOT_ENTER=0 build). */
+/* Format 0's root entry (1, what the kernel does: its slab test skipped; 0:
+ * tested first, as the kernel did before round 6). */
 int orc_accel_root(int on) {
     g_root_enter = on < 0 ? 0 : on;
     return 0;
@@ -506,7 +506,7 @@ static int accel_walk(const scene* s, ray r, float* closest_t, int* hit_index, v
     uint64_t leaf_visits = 0;
     const size_t WS = g_fmt ? 4 : 8;
     for (int k = 0; k < g_root_enter && !g_fmt && !leaf && g_slots > 1; ++k) {
-        /* format 0: the walk starts inside the root (rt_trace.hip RT_ROOT_ENTER):
+        /* format 0: the walk starts inside the root (rt_trace.hip, DevScene::root_enter):
          * its box is not tested; it counts as visited and entered (a study:
          * g_root_enter > 1 enters the first child the same way, and so on) */
         cnt->node_visits++;

@@ -198,13 +198,31 @@ def test_jni_shim_matches_java_and_header():
     assert calls <= declared, calls - declared
 
 
+# The 32 settable options, "kernel" and the 12 read-only names.
+OPTION_NAMES = {
+    "coop_lanes", "extensions", "walk", "coop_window", "coop_walk", "block_waves", "heavy_first", "heavy_tiles",
+    "heavy_factor", "heavy_pixels", "heavy_pixel_factor", "reuse_order", "heavy_cap", "async_slots", "copy_streams",
+    "concurrent_launches", "learn_cost", "order_frames", "order_split", "learn_alone", "xcd_order", "accel_octants",
+    "learn_device", "leaf_align", "accel", "split_bounce", "accel_half", "accel_wide", "heavy_stream", "graph",
+    "diag", "wave_tile",
+    "kernel",
+    "wave_tile_used", "coop_window_used", "accel_half_used", "accel_wide_used", "accel_used", "walk_bytes",
+    "leaf_align_used", "heavy_pixels_used", "heavy_tiles_used", "plain_kernels", "hw_queues", "queues_short",
+}
+
+
 def test_every_option_is_documented():
     """Every option name rt_set_option / rt_get_option accepts
     (csrc/rt_runtime.hip) is documented in include/rtamd.h."""
     import re
     src = open(os.path.join(ROOT, "3d-ray-tracer-vulkan_amd", "csrc", "rt_runtime.hip")).read()
     hdr = open(os.path.join(ROOT, "include", "rtamd.h")).read()
-    names = set(re.findall(r'std::strcmp\(name, "([a-z0-9_]+)"\)', src))
+    # the settable options are the rows of the kOptions table; "kernel" and the
+    # read-only names are compared one by one
+    names = set(re.findall(r'\b(?:in_range|one_of)\("([a-z0-9_]+)", &rt_ctx::', src))
+    names |= set(re.findall(r'\bis\("([a-z0-9_]+)"\)', src))
+    names |= set(re.findall(r'std::strcmp\(name, "([a-z0-9_]+)"\)', src))
     assert len(names) > 20
+    assert names >= OPTION_NAMES, sorted(OPTION_NAMES - names)
     missing = sorted(n for n in names if f'"{n}"' not in hdr)
     assert not missing, missing

@@ -29,7 +29,7 @@ R04_LINES = [("r4b", "bench.json"), ("r4b", "bench_orbit.json"), ("r4b", "prof3.
              # config 5), PMC of the same session
              ("r4s", "bench.json"), ("r4s", "bench_orbit.json"), ("r4s", "prof3.json"), ("r4s", "prof5.json"),
              ("r4s", "bench_cfg5.json"),
-             # + the walk's buffer loads (RT_CHAIN 2): the shipped build
+             # + the walk's buffer loads (rt_trace.hip wbuf): the shipped build
              ("r4u", "bench.json"), ("r4u", "bench_orbit.json"), ("r4u", "prof3.json"), ("r4u", "prof5.json"),
              ("r4u", "bench_cfg5.json"),
              # + 16x4 tiles for scenes past 32 MB of records (config 5)
