@@ -435,12 +435,14 @@ def _adversarial():
 
 
 @pytest.mark.parametrize("name", ["slivers", "fine_mesh", "grazing", "grazing_cube", "far_origin_near",
-                                  "far_origin_far", "far_origin_neg", "near_camera"])
+                                  "far_origin_far", "far_origin_neg", "near_camera", "far_origin_1e5_near",
+                                  "far_origin_1e5_far", "far_origin_1e6_near", "far_origin_1e6_far",
+                                  "far_origin_1e6_neg", "slivers_1e6", "fine_mesh_1e6", "grazing_1e6"])
 def test_adversarial_scenes(name):
     """Geometry built to approach the accel walk's exactness margin (verdict
     r05, next #2; tools/accel_adversarial.py): needle slivers, a fine mesh
     whose hits have |det| near the shader's 1e-5 cut, grazing rays on a
-    tilted ground and along the cube's faces, meshes at +-1e4, triangles
+    tilted ground and along the cube's faces, meshes at +-1e4 to +-1e6, triangles
     1e-3 from the eye.  Small versions: the model's frame equals the
     oracle's, and the audit finds no segment outside the margin the walk
     applies (thin triangles' boxes carry wider ones: accel_build.h

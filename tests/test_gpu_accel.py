@@ -196,14 +196,16 @@ def _adversarial():
 
 @pytest.mark.parametrize("nl", [1, 8, HALF8, WIDE])
 @pytest.mark.parametrize("name", ["slivers", "fine_mesh", "grazing", "grazing_cube", "far_origin_near",
-                                  "far_origin_far", "far_origin_neg", "near_camera"])
+                                  "far_origin_far", "far_origin_neg", "near_camera", "far_origin_1e5_near",
+                                  "far_origin_1e5_far", "far_origin_1e6_near", "far_origin_1e6_far",
+                                  "far_origin_1e6_neg", "slivers_1e6", "fine_mesh_1e6", "grazing_1e6"])
 def test_accel_adversarial_scenes(acc, name, nl):
     """The adversarial scenes of the margin audit (tools/accel_adversarial.py,
     DESIGN.md §4a) on the GPU: needles whose rounded t lies up to 17 margins
     before their box (the forced records of accel_build.h kAccelForce), a fine
     shell with |det| near the shader's 1e-5 cut, grazing rays, meshes at
-    +-1e4, triangles 1e-3 from the eye.  Small versions (scale 0.3, 240 x 135,
-    4 bounces): frames equal the oracle's, counters the accel model's."""
+    +-1e4 to +-1e6, triangles 1e-3 from the eye.  Small versions (scale 0.3,
+    240 x 135, 4 bounces): frames equal the oracle's, counters the accel model's."""
     from rtamd import build_buffers, configs
     A = _adversarial()
     verts, mats, (eye, at), vfov = A.SCENES[name](0.3)

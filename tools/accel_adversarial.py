@@ -21,7 +21,9 @@ the geometry is built to approach it:
                its top face;
   far_origin   config 2's cube and plane and a procedural shell translated to
                +-1e4 (coordinates whose float ulp is 2^-10, the margin's
-               absolute part), camera translated with them, near and far;
+               absolute part), camera translated with them, near and far; the
+               same at +-1e5 and +-1e6, and slivers, fine_mesh and grazing
+               shifted whole by (1e6, -1e6, 1e6) (translated);
   near_camera  small triangles 1e-3 - 1e-2 in front of the camera (t at
                T_MIN = 0.001, where the absolute part of the margin dominates).
 
@@ -150,6 +152,21 @@ def scene_near_camera(scale=1.0, seed=16):
     return verts, mats, (tuple(eye), (0.0, 0.0, 0.0)), 50.0
 
 
+def translated(name, offset):
+    """Scene `name` and its camera shifted by `offset` (the vertices in double,
+    before the builder rounds them to float as it rounds every scene's)."""
+    def scene(scale=1.0):
+        verts, mats, (eye, at), vfov = SCENES[name](scale)
+        o = np.array(offset, np.float64)
+        return (np.asarray(verts, np.float64) + np.tile(o, 3), mats,
+                (tuple(o + np.array(eye)), tuple(o + np.array(at))), vfov)
+    return scene
+
+
+def _far(mag, near, signs=(1.0, -1.0, 1.0)):
+    return lambda scale=1.0: scene_far_origin(scale, offset=tuple(s * mag for s in signs), near=near)
+
+
 SCENES = {
     "slivers": scene_slivers,
     "fine_mesh": scene_fine_mesh,
@@ -159,6 +176,17 @@ SCENES = {
     "far_origin_far": lambda scale=1.0: scene_far_origin(scale, near=False),
     "far_origin_neg": lambda scale=1.0: scene_far_origin(scale, offset=(-1.0e4, 1.0e4, -1.0e4), near=True),
     "near_camera": scene_near_camera,
+    # past +-1e4 (verdict r06, next #1): the camera moves with the geometry, so
+    # o - v0 and b - o stay exact at any offset; what changes is the ulp of the
+    # coordinates themselves (2^-7 at 1e5, 2^-4 at 1e6)
+    "far_origin_1e5_near": _far(1.0e5, True),
+    "far_origin_1e5_far": _far(1.0e5, False),
+    "far_origin_1e6_near": _far(1.0e6, True),
+    "far_origin_1e6_far": _far(1.0e6, False),
+    "far_origin_1e6_neg": _far(1.0e6, True, (-1.0, 1.0, -1.0)),
+    "slivers_1e6": translated("slivers", (1.0e6, -1.0e6, 1.0e6)),
+    "fine_mesh_1e6": translated("fine_mesh", (1.0e6, -1.0e6, 1.0e6)),
+    "grazing_1e6": translated("grazing", (1.0e6, -1.0e6, 1.0e6)),
 }
 
 
