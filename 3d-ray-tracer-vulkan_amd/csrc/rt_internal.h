@@ -187,6 +187,14 @@ struct TraceArgs {
     int      q_grid = 0;        // kernel 2's one-wave workgroups
     void*    q_temp = nullptr;  // the scan's temporary storage (rocPRIM), q_temp_bytes
     size_t   q_temp_bytes = 0;
+    // Query launch (launch_query; rtamd.h rt_query_rays_device, rt_render_hits_device):
+    // lane i % 64 of wave i / 64 walks ray i of ray_in (2 float4 per rt_ray: origin.xyz, t_max;
+    // dir.xyz, reserved), or with ray_in null the primary ray of its pixel, once, and writes its
+    // rt_hit (2 float4: t, tri, normal.xy; normal.z, pos.xyz) to hit_out.  Appended after every
+    // field the render kernels read, so their argument offsets are the ones they always had.
+    const float4* ray_in = nullptr;
+    float4*  hit_out = nullptr;
+    int      any_hit = 0;       // RT_QUERY_ANY: a lane's walk stops at its first consistent hit
 };
 
 // Host-side compact-scene build from the reference records; validates the
@@ -240,6 +248,12 @@ hipError_t learn_on_device(const LearnParams& lp, const unsigned long long* rec,
 // Kernel launcher (rt_trace.hip).  *kernels (nullable) = the kernels it
 // enqueued (2 when the heavy tiles run as a launch of their own).
 hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels = nullptr);
+
+// The query launch (rt_trace.hip): a.scene is the accel format-0 scene or a
+// reference-records scene (n_layouts 0); tw x th rays (th 1, wave_tile 3 for a
+// ray batch) in a 1-D grid of one-wave workgroups.  One kernel, no learned
+// order, no heavy pixels.
+hipError_t launch_query(const TraceArgs& a, hipStream_t stream);
 
 void set_error(const char* fmt, ...);
 

@@ -305,6 +305,12 @@ struct PerDevice {
     // TraceArgs::q_slots), grown to the largest launch seen on that stream
     struct Slots { hipStream_t s; char* base; int waves; size_t temp_bytes; };
     std::vector<Slots> slots;
+    // queries (rt_query_rays, rt_pick): the host forms' device staging, rays
+    // then hits, grown to the largest batch; and L(0) of the reference's own
+    // tree, which a query over an accel scene's reference records starts from
+    char*        d_query = nullptr;
+    size_t       query_cap = 0;      // bytes
+    int          ref_root_leaf = 0;
 };
 
 static constexpr size_t kMaxOrders = 16;
@@ -1197,6 +1203,7 @@ int rt_destroy(rt_ctx* ctx) {
         p.slots.clear();
         if (p.d_accum) (void)hipFree(p.d_accum);
         if (p.d_spheres) (void)hipFree(p.d_spheres);
+        if (p.d_query) (void)hipFree(p.d_query);
         if (p.d_rgba) (void)hipFree(p.d_rgba);
         if (p.d_rad) (void)hipFree(p.d_rad);
         if (p.ev0) (void)hipEventDestroy(p.ev0);
@@ -1395,6 +1402,7 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
         // launch stream (non-blocking) reads the scene
         if (e == hipSuccess) e = hipDeviceSynchronize();
         p.scene = s;
+        p.ref_root_leaf = hs.root_leaf;
         if (e != hipSuccess) {
             set_error("rt_upload_scene: device %d: %s", p.device, hipGetErrorString(e));
             free_scene(p);
@@ -1526,6 +1534,175 @@ int rt_render_tile_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int 
         RT_HIP_CHECK(hipEventSynchronize(p.ev1));
         return collect_stats(ctx, p, (uint64_t)tile_w * (uint64_t)tile_h, stats, false);
     }
+    return RT_OK;
+}
+
+// ------------------------------------------------------------------ queries --
+// A query launch touches none of the render state: no learned order, graph,
+// async slot or accumulation sum is read or written, and its kernel is not
+// counted in plain_kernels (a profiler trace is cut by that count).
+static int run_query(rt_ctx* ctx, PerDevice& p, TraceArgs& a, uint64_t n, unsigned flags, hipStream_t s,
+                     rt_stats* stats) {
+    a.scene = p.scene;
+    if (p.scene.n_layouts > 0 && (p.scene.half || p.scene.wide)) {
+        // accel_half / accel_wide scenes: over the reference's records, which
+        // lie beside every accel scene for the fallback
+        DevScene& r = a.scene;
+        r.walk = p.scene.walk_ref;
+        r.end2 = r.end = p.scene.end2_ref;
+        r.padded = p.scene.ref_padded;
+        r.root_leaf = p.ref_root_leaf;
+        r.n_layouts = r.layout_slots = r.half = r.wide = r.root_enter = r.root_first_leaf = 0;
+    }
+    a.scene.spheres = nullptr;                           // queries see triangles only
+    a.scene.n_spheres = 0;
+    a.scene.oct_mask = ctx->accel_octants;
+    a.n_frames = 1;
+    a.max_bounces = 1;
+    a.band_stride = 1; a.band_off = 0;
+    a.band_list = nullptr;
+    a.list_stride = 0;
+    a.out_rgba = nullptr;
+    a.out_rad = nullptr;
+    a.counters = stats ? p.d_counters : nullptr;
+    a.diag = nullptr;
+    a.coop_lanes = a.scene.n_layouts ? 0 : (ctx->coop_lanes >= 0 ? ctx->coop_lanes : 1);
+    a.ext = 0;
+    a.sky_enabled = 1;
+    a.frame_count = 0;
+    a.accum = nullptr;
+    a.walk = 2;
+    a.block_waves = 1;
+    a.tile_order = nullptr;
+    a.tiles_x = 0;
+    a.split_n = a.heavy_tiles = a.heavy_fused = a.n_heavy_px = 0;
+    a.heavy_px = nullptr;
+    a.tile_mask = nullptr;
+    a.diag_lane = nullptr;
+    a.aux_stream = nullptr;
+    a.ev_fork = a.ev_join = nullptr;
+    a.coop_walk = 0;
+    a.coop_win = 64;
+    a.any_hit = (flags & RT_QUERY_ANY) ? 1 : 0;
+    if (stats) {
+        RT_HIP_CHECK(hipMemsetAsync(p.d_counters, 0, sizeof(Counters), s));
+        RT_HIP_CHECK(hipEventRecord(p.ev0, s));
+    }
+    RT_HIP_CHECK(launch_query(a, s));
+    if (stats) {
+        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
+        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
+        return collect_stats(ctx, p, n, stats, false);
+    }
+    return RT_OK;
+}
+
+static int query_staging(PerDevice& p, size_t bytes) {
+    if (bytes <= p.query_cap) return RT_OK;
+    if (p.d_query) {
+        RT_HIP_CHECK(hipStreamSynchronize(p.stream));    // (the host forms are synchronous: nothing in flight)
+        (void)hipFree(p.d_query);
+    }
+    p.d_query = nullptr;
+    p.query_cap = 0;
+    const hipError_t e = hipMalloc(&p.d_query, bytes);
+    if (e != hipSuccess) {
+        set_error("query staging: %zu bytes: %s", bytes, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+    }
+    p.query_cap = bytes;
+    return RT_OK;
+}
+
+int rt_query_rays_device(rt_ctx* ctx, const rt_ray* d_rays, size_t n_rays, uint32_t flags, rt_hit* d_hits,
+                         void* stream, rt_stats* stats) {
+    if (!ctx || !d_rays || !d_hits) { set_error("rt_query_rays_device: null context or buffer"); return RT_ERR_INVALID_ARG; }
+    if (n_rays < 1 || n_rays > ((size_t)1 << 26)) {
+        set_error("rt_query_rays_device: n_rays must be in [1, 2^26], got %zu", n_rays);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u) {
+        set_error("rt_query_rays_device: d_rays and d_hits must be 16-byte aligned");
+        return RT_ERR_INVALID_ARG;
+    }
+    if (flags & ~(uint32_t)RT_QUERY_ANY) { set_error("rt_query_rays_device: unknown flags 0x%x", flags); return RT_ERR_INVALID_ARG; }
+    if (!ctx->has_scene) { set_error("rt_query_rays_device: no scene uploaded"); return RT_ERR_NO_SCENE; }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    TraceArgs a;
+    a.cams[0] = CamF{};
+    a.width = (int)n_rays; a.height = 1;
+    a.x0 = 0; a.y0 = 0; a.tw = (int)n_rays; a.th = 1;
+    a.band_h = 1;
+    a.wave_tile = 3;                                     // 64 x 1: ray i is lane i % 64 of wave i / 64
+    a.ray_in = reinterpret_cast<const float4*>(d_rays);
+    a.hit_out = reinterpret_cast<float4*>(d_hits);
+    return run_query(ctx, p, a, (uint64_t)n_rays, flags, static_cast<hipStream_t>(stream), stats);
+}
+
+int rt_query_rays(rt_ctx* ctx, const rt_ray* rays, size_t n_rays, uint32_t flags, rt_hit* hits, rt_stats* stats) {
+    if (!ctx || !rays || !hits) { set_error("rt_query_rays: null context or buffer"); return RT_ERR_INVALID_ARG; }
+    if (n_rays < 1 || n_rays > ((size_t)1 << 26)) {
+        set_error("rt_query_rays: n_rays must be in [1, 2^26], got %zu", n_rays);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (!ctx->has_scene) { set_error("rt_query_rays: no scene uploaded"); return RT_ERR_NO_SCENE; }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    const size_t rb = n_rays * sizeof(rt_ray), hb = n_rays * sizeof(rt_hit);
+    if (int rc = query_staging(p, rb + hb)) return rc;
+    RT_HIP_CHECK(hipMemcpyAsync(p.d_query, rays, rb, hipMemcpyHostToDevice, p.stream));
+    int rc = rt_query_rays_device(ctx, reinterpret_cast<const rt_ray*>(p.d_query), n_rays, flags,
+                                  reinterpret_cast<rt_hit*>(p.d_query + rb), p.stream, stats);
+    if (rc) return rc;
+    RT_HIP_CHECK(hipMemcpyAsync(hits, p.d_query + rb, hb, hipMemcpyDeviceToHost, p.stream));
+    RT_HIP_CHECK(hipStreamSynchronize(p.stream));
+    return RT_OK;
+}
+
+int rt_render_hits_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int x0, int y0,
+                          int tile_w, int tile_h, uint32_t flags, rt_hit* d_hits, void* stream, rt_stats* stats) {
+    int rc = check_render_args(ctx, cam, width, height, 1, "rt_render_hits_device");
+    if (rc) return rc;
+    if (tile_w < 1 || tile_h < 1 || x0 < 0 || y0 < 0 || x0 + tile_w > width || y0 + tile_h > height) {
+        set_error("rt_render_hits_device: tile (%d,%d %dx%d) outside the %dx%d frame", x0, y0, tile_w, tile_h, width,
+                  height);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (!d_hits || ((uintptr_t)d_hits & 15u)) {
+        set_error("rt_render_hits_device: d_hits must be a 16-byte aligned device pointer");
+        return RT_ERR_INVALID_ARG;
+    }
+    if (flags & ~(uint32_t)RT_QUERY_ANY) { set_error("rt_render_hits_device: unknown flags 0x%x", flags); return RT_ERR_INVALID_ARG; }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    TraceArgs a;
+    a.cams[0] = cam_from_ubo(cam);
+    a.width = width; a.height = height;
+    a.x0 = x0; a.y0 = y0; a.tw = tile_w; a.th = tile_h;
+    a.band_h = tile_h;
+    a.wave_tile = wave_tile_of(ctx, p);                  // the render's wave tiles: the same walks side by side
+    a.ray_in = nullptr;
+    a.hit_out = reinterpret_cast<float4*>(d_hits);
+    return run_query(ctx, p, a, (uint64_t)tile_w * (uint64_t)tile_h, flags, static_cast<hipStream_t>(stream), stats);
+}
+
+int rt_pick(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int x, int y, rt_hit* out_hit) {
+    int rc = check_render_args(ctx, cam, width, height, 1, "rt_pick");
+    if (rc) return rc;
+    if (!out_hit) { set_error("rt_pick: null out_hit"); return RT_ERR_INVALID_ARG; }
+    if (x < 0 || y < 0 || x >= width || y >= height) {
+        set_error("rt_pick: pixel (%d,%d) outside the %dx%d frame", x, y, width, height);
+        return RT_ERR_INVALID_ARG;
+    }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    if (int rs = query_staging(p, sizeof(rt_hit))) return rs;
+    rc = rt_render_hits_device(ctx, cam, width, height, x, y, 1, 1, 0, reinterpret_cast<rt_hit*>(p.d_query), p.stream,
+                               nullptr);
+    if (rc) return rc;
+    RT_HIP_CHECK(hipMemcpyAsync(out_hit, p.d_query, sizeof(rt_hit), hipMemcpyDeviceToHost, p.stream));
+    RT_HIP_CHECK(hipStreamSynchronize(p.stream));
     return RT_OK;
 }
 

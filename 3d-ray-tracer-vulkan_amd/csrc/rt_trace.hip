@@ -18,7 +18,9 @@
 // the rules that keep the reference's closest hit (accel_enter, accel_take) and
 // the reference-order fallback; kFeatHalf (option accel_half) reads its 16-B
 // half-precision internal records; kFeatQ1 / kFeatQ2 (option split_bounce)
-// split a frame's paths over two kernels (§4b).
+// split a frame's paths over two kernels (§4b); kFeatQuery (launch_query, §4e)
+// walks a caller's rays, or the primary rays, once and stores each ray's hit
+// record instead of shading it (rtamd.h rt_query_rays_device).
 //
 // The kernel, trace_simple: one lane = one pixel for its whole path; a wave
 // is a tile of 64 pixels (the reference's 8x8 dispatch shape, or 16x4 / 32x2
@@ -890,7 +892,19 @@ constexpr int kFeatWide = 1024;   // option accel_wide (with kFeatAccel): the 4-
                                   //   children ordered by t_enter, a per-lane LDS stack (wide_step)
 constexpr int kFeatAccel = 512;   // option accel: the accel records and rules, packed records, the
                                   //   reference-order fallback
+constexpr int kFeatQuery = 16384; // query mode (launch_query): a lane's ray comes from
+                                  //   TraceArgs::ray_in (or is its pixel's primary ray), is walked once
+                                  //   from its own t_max, and its hit record is stored instead of shading
 constexpr unsigned kHeavyLaneMark = kLearnHeavyMark;   // rt_internal.h
+
+// A query's hit record (rtamd.h rt_hit): (t, tri, normal.xy), (normal.z, pos.xyz).
+__device__ __forceinline__ void store_hit(float4* h, float t, int tri, V3 n, V3 p) {
+    h[0] = make_float4(t, __int_as_float(tri), n.x, n.y);
+    h[1] = make_float4(n.z, p.x, p.y, p.z);
+}
+__device__ __forceinline__ bool finite3(V3 a) {
+    return fabsf(a.x) < __builtin_inff() && fabsf(a.y) < __builtin_inff() && fabsf(a.z) < __builtin_inff();
+}
 
 // One pixel of a heavy tile, the whole wave on it (option heavy_fused, the
 // workgroups in front of the tile workgroups of the same launch): every
@@ -985,6 +999,7 @@ void trace_simple(TraceArgs a) {
     constexpr bool WIDE = ACC && (FEAT & kFeatWide) != 0;
     constexpr bool PAD = !ACC && ((FEAT & kFeatPad) || (FEAT & (kFeatExt | kFeatFrontier)) || !(FEAT & kFeatCoopTail));
     constexpr bool Q1 = (FEAT & kFeatQ1) != 0, Q2 = (FEAT & kFeatQ2) != 0;
+    constexpr bool QRY = (FEAT & kFeatQuery) != 0;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     // frontier_walk's per-wave frontiers (kFCap entries per wave; dynamic LDS,
@@ -1007,6 +1022,10 @@ void trace_simple(TraceArgs a) {
     // order are traced one pixel per wave (64 workgroups per tile): the wave's
     // single live lane walks every segment cooperatively (frontier walk).
     int bx = blockIdx.x, by = blockIdx.y, sub = -1;
+    if (QRY) {                                           // a 1-D grid over the wave tiles, row by row
+        by = bx / a.tiles_x;
+        bx -= by * a.tiles_x;
+    }
     unsigned long long skip_lanes = 0;                   // heavy pixels this tile wave leaves out
     // Diagnostic record of this wave and the tile of its per-pixel walk
     // lengths (diag builds): the wave's index in the grid, except in a fused
@@ -1096,6 +1115,8 @@ void trace_simple(TraceArgs a) {
     V3 att = {1.0f, 1.0f, 1.0f};
     bool alive = pixel;
     int b0 = 0;
+    float tmax = kTMax;               // query: the ray's t_max, where its closest_t starts
+    bool refq = false;                // query: a non-unit direction, walked in the reference's order
     if (Q2) {
         // path i of the slot order: source wave w with prefix[w] <= i < prefix[w + 1]
         const unsigned i = q_k * 64u + (unsigned)lane;
@@ -1119,7 +1140,24 @@ void trace_simple(TraceArgs a) {
             lx = pq - lyo * a.tw;
         }
     }
-    if (pixel) {
+    if (QRY && a.ray_in) {
+        // Ray lx of the batch (64 x 1 wave tiles: ray i is lane i % 64 of wave
+        // i / 64), two 16-B loads.  t_max >= T_MAX or NaN is T_MAX.  A ray with
+        // a non-finite component or an all-zero direction is not walked
+        // (tri = -2).  The accel walk's margins were audited for unit
+        // directions: any other is walked over the reference's records.
+        if (pixel) {
+            const float4 r0 = a.ray_in[2 * (size_t)lx], r1 = a.ray_in[2 * (size_t)lx + 1];
+            o = {r0.x, r0.y, r0.z};
+            d = {r1.x, r1.y, r1.z};
+            if (r0.w < kTMax) tmax = r0.w;
+            if (!finite3(o) || !finite3(d) || (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f)) {
+                store_hit(a.hit_out + 2 * (size_t)lx, 0.0f, -2, V3{0.f, 0.f, 0.f}, V3{0.f, 0.f, 0.f});
+                alive = false;
+            }
+            refq = ACC && fabsf(vdot(d, d) - 1.0f) > kRelaxAbs;
+        }
+    } else if (pixel) {
         const int x = a.x0 + lx, y = frame_row(a, fr_i, ly);
         if ((FEAT & kFeatExt) && (a.ext & kExtAccumulate)) {
             // extension: a new sample per frame; frame 0 is the reference's seed (:164)
@@ -1133,7 +1171,7 @@ void trace_simple(TraceArgs a) {
     // The bounce loop (:179) is wave-uniform: a lane whose path has ended
     // stays in it with alive = false, so the cooperative tail below can use
     // every lane of the wave.
-    for (int b = b0; b < a.max_bounces; ++b) {
+    for (int b = b0; b < (QRY ? 1 : a.max_bounces); ++b) {   // (a query walks its ray once)
         if (__ballot(alive) == 0) break;
         if (Q1 && b == a.split_bounce) {
             // Split kernel 1: the paths still alive leave for this wave's 64
@@ -1149,7 +1187,7 @@ void trace_simple(TraceArgs a) {
             alive = false;
             break;
         }
-        float closest = kTMax;
+        float closest = QRY ? tmax : kTMax;
         int hit = -1;
         const V3 inv = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};              // :89
         // The walk's position: n = the next node the reference would visit
@@ -1165,7 +1203,8 @@ void trace_simple(TraceArgs a) {
             lend = n + a.scene.layout_slots;
         }
         bool nleaf = a.scene.root_leaf != 0;
-        bool walking = alive && end > 0;
+        const bool own = alive && !(QRY && refq);       // this walk is the lane's (not left to the re-walk below)
+        bool walking = own && end > 0;
         // Format 0 (round 6): the walk starts inside the root.  Entering an
         // internal box whose slab test would fail only tests its children,
         // which fail it too (their boxes lie inside), so results are the
@@ -1174,7 +1213,7 @@ void trace_simple(TraceArgs a) {
         if (ACC && !HALF && !WIDE && a.scene.root_enter) {
             n += 1;
             nleaf = ((a.scene.root_first_leaf >> oct) & 1) != 0;
-            if (COUNT && alive) c_node += 2;
+            if (COUNT && own) c_node += 2;
         }
         // the wide walk (kFeatWide): the record to read next (a child link:
         // index | flags), the lane's stack depth, and an overflowed stack
@@ -1183,7 +1222,7 @@ void trace_simple(TraceArgs a) {
         bool wovf = false;
         if (COUNT && alive) {
             ++c_seg;
-            if (end > 0) ++c_node;                                       // the root visit
+            if (end > 0 && own) ++c_node;                                // the root visit
         }
         {
             // The per-node walk: one dependent load per visit, lanes in lockstep.
@@ -1347,6 +1386,8 @@ void trace_simple(TraceArgs a) {
                     if (!BYTES) n = nxt;
                     nleaf = nl;
                     walking = inb;
+                    // RT_QUERY_ANY: the first hit closest mode would keep as consistent ends the walk
+                    if (QRY && a.any_hit && hit >= 0 && !incons) walking = false;
                 }
                 if (WALK == 0 || HALF) walking = n < (ACC ? lend : wend);
                 if ((FEAT & kFeatCoopTail) && __popcll(__ballot(walking)) <= coop_lanes) break;
@@ -1407,14 +1448,15 @@ void trace_simple(TraceArgs a) {
             // is the one case where the reference's result depends on its
             // visit order; such a segment is walked again, in the reference's
             // order over the reference's records, by the whole wave.
-            uint64_t redo = __ballot(alive && ((hit >= 0 && incons) || (WIDE && wovf)));
+            // (a query's non-unit ray is walked here only, from its own t_max)
+            uint64_t redo = __ballot(alive && ((hit >= 0 && incons) || (WIDE && wovf) || (QRY && refq)));
             while (redo != 0) {
                 const int L = __ffsll((long long)redo) - 1;
                 redo &= redo - 1;
                 const V3 bo = {lane_f(o.x, L), lane_f(o.y, L), lane_f(o.z, L)};
                 const V3 bd = {lane_f(d.x, L), lane_f(d.y, L), lane_f(d.z, L)};
                 const V3 bi = {lane_f(inv.x, L), lane_f(inv.y, L), lane_f(inv.z, L)};
-                float bc = kTMax;
+                float bc = QRY ? lane_f(tmax, L) : kTMax;
                 int bh = -1;
                 bool bx = false;
                 unsigned long long cn = 1, ct = 0;   // the reference walk's root visit
@@ -1432,7 +1474,17 @@ void trace_simple(TraceArgs a) {
         }
         if ((FEAT & kFeatExt) && alive && a.scene.n_spheres > 0)
             sphere_tests(a.scene.spheres, a.scene.n_spheres, o, d, closest, hit);   // extension: spheres
-        if (alive) {
+        if (QRY && alive) {
+            // the hit record instead of shading: closest_t, the triangle, the
+            // normal of :124-125 and ray_at (:77-79); a miss: the ray's t_max
+            float4* h = a.hit_out + 2 * ((size_t)lyo * (size_t)a.tw + (size_t)lx);
+            if (hit >= 0)
+                store_hit(h, closest, hit, hit_normal(a.scene.norms, hit, d), vadd(o, vscale(d, closest)));
+            else
+                store_hit(h, tmax, -1, V3{0.f, 0.f, 0.f}, V3{0.f, 0.f, 0.f});
+            alive = false;
+        }
+        if (!QRY && alive) {
             // A path that ends here writes its pixel now, so its final colour
             // is not carried (in registers) through the remaining bounces.
             V3 fin = {0.0f, 0.0f, 0.0f};
@@ -1469,7 +1521,7 @@ void trace_simple(TraceArgs a) {
         }
     }
     // A path still alive here ran no bounce at all (max_bounces 0): black.
-    if (alive) finish_pixel<FEAT>(a, lx, lyo, V3{0.0f, 0.0f, 0.0f});
+    if (!QRY && alive) finish_pixel<FEAT>(a, lx, lyo, V3{0.0f, 0.0f, 0.0f});
     q_k += gridDim.x;
   } while (Q2 && q_k * 64u < q_total);
     if (COUNT) flush_counters(a.counters, c_seg, c_node, c_tri, c_mat);
@@ -1678,6 +1730,37 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels) {
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamWaitEvent(stream, a.ev_join, 0);
         return e;
+    }
+    return hipGetLastError();
+}
+
+// The query kernels: trace_simple in query mode over option accel's format-0
+// records (8 or 1 layouts), or over the reference's walk records (packed or
+// with pad slots: the one variant reads the pad bits, which packed records
+// leave zero) with the cooperative tail, each with and without counters.
+hipError_t launch_query(const TraceArgs& a, hipStream_t stream) {
+    if (a.scene.half || a.scene.wide || a.walk != 2 || !a.hit_out) {
+        set_error("query launch over format-%d records, walk %d", a.scene.wide ? 2 : a.scene.half, a.walk);
+        return hipErrorInvalidValue;                     // (run_query hands such scenes' reference records in)
+    }
+    const int tw_w = 8 << a.wave_tile, th_w = 8 >> a.wave_tile;
+    TraceArgs ao = a;
+    ao.n_frames = 1;
+    ao.block_waves = 1;
+    ao.tiles_x = (a.tw + tw_w - 1) / tw_w;
+    ao.tiles_y = (a.th + th_w - 1) / th_w;
+    ao.tile_order = nullptr;
+    ao.split_n = 0;
+    ao.diag = nullptr;
+    ao.ext = 0;
+    const dim3 grid((unsigned)ao.tiles_x * (unsigned)ao.tiles_y), block(64);
+    constexpr int FA = kFeatAccel | kFeatQuery, FR = kFeatCoopTail | kFeatPad | kFeatQuery;
+    if (a.scene.n_layouts > 0) {
+        if (a.counters) hipLaunchKernelGGL((trace_simple<true, false, FA, 2>), grid, block, 0, stream, ao);
+        else hipLaunchKernelGGL((trace_simple<false, false, FA, 2>), grid, block, 0, stream, ao);
+    } else {
+        if (a.counters) hipLaunchKernelGGL((trace_simple<true, false, FR, 2>), grid, block, 0, stream, ao);
+        else hipLaunchKernelGGL((trace_simple<false, false, FR, 2>), grid, block, 0, stream, ao);
     }
     return hipGetLastError();
 }

@@ -104,6 +104,7 @@ struct Builder {
     float* out_v;
     float* out_m;
     unsigned char* out_n;
+    uint32_t* out_src = nullptr;   // rt_build_scene_map: the input triangle of every flattened one
     int max_par_depth;
 
     void write_node(size_t idx, const Box& b, int32_t data, int32_t count) {
@@ -129,6 +130,7 @@ struct Builder {
             o[4 * k + 3] = 0.0f;
         }
         std::memcpy(out_m + flat_idx * 4, mats + (size_t)tri * 4, 16);
+        if (out_src) out_src[flat_idx] = tri;
     }
 
     // buildRecursive(objects, start, end) + flattenRecursive of the node it
@@ -191,6 +193,13 @@ int rt_bvh_layout_size(size_t n_tris, size_t* n_nodes, size_t* n_flat_tris) {
 int rt_build_scene(const double* tri_verts, const float* tri_mats, size_t n_tris,
                    uint64_t axis_seed, int n_threads,
                    float* out_vertices, float* out_materials, void* out_nodes) {
+    return rt_build_scene_map(tri_verts, tri_mats, n_tris, axis_seed, n_threads, out_vertices, out_materials,
+                              out_nodes, nullptr);
+}
+
+int rt_build_scene_map(const double* tri_verts, const float* tri_mats, size_t n_tris,
+                       uint64_t axis_seed, int n_threads,
+                       float* out_vertices, float* out_materials, void* out_nodes, uint32_t* out_source) {
     if (n_tris == 0) return RT_OK;
     if (!tri_verts || !tri_mats || !out_vertices || !out_materials || !out_nodes) {
         set_error("rt_build_scene: null pointer");
@@ -205,6 +214,7 @@ int rt_build_scene(const double* tri_verts, const float* tri_mats, size_t n_tris
         b.out_v = out_vertices;
         b.out_m = out_materials;
         b.out_n = static_cast<unsigned char*>(out_nodes);
+        b.out_src = out_source;
         unsigned hw = n_threads > 0 ? (unsigned)n_threads : std::max(1u, std::thread::hardware_concurrency());
         int pd = 0;
         while ((1u << pd) < hw && pd < 8) ++pd;

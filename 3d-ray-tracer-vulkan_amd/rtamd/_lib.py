@@ -38,6 +38,7 @@ EXPORTED = (
     "rt_render_batch_device", "rt_band_list_rows", "rt_render_batch_lists_device", "rt_band_lists_rows",
     "rt_render_poll", "rt_accel_records", "rt_abi_version", "rt_pack_rgb", "rt_unpack_rgb",
     "rt_build_id", "rt_render_batch_rect_device", "rt_render_batch_runs_device",
+    "rt_query_rays_device", "rt_query_rays", "rt_render_hits_device", "rt_pick", "rt_build_scene_map",
 )
 
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
@@ -108,7 +109,18 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Ray(C.Structure):                 # rt_ray
+    _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("dir", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class Hit(C.Structure):                 # rt_hit
+    _fields_ = [("t", C.c_float), ("tri", C.c_int32), ("normal", C.c_float * 3), ("pos", C.c_float * 3)]
+
+
+RT_QUERY_ANY = 1
+
 assert C.sizeof(CameraUBO) == 80
+assert C.sizeof(Ray) == 32 and C.sizeof(Hit) == 32
 
 _lock = threading.Lock()
 _lib = None
@@ -178,6 +190,12 @@ def lib() -> C.CDLL:
                 "rt_build_id": (C.c_char_p, []),
                 "rt_pack_rgb": (i32, [vp, vp, sz, vp]),
                 "rt_unpack_rgb": (i32, [vp, vp, sz, vp]),
+                "rt_query_rays_device": (i32, [vp, vp, sz, C.c_uint32, vp, vp, C.POINTER(Stats)]),
+                "rt_query_rays": (i32, [vp, vp, sz, C.c_uint32, vp, C.POINTER(Stats)]),
+                "rt_render_hits_device": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, i32, i32, i32, C.c_uint32,
+                                                vp, vp, C.POINTER(Stats)]),
+                "rt_pick": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, i32, C.POINTER(Hit)]),
+                "rt_build_scene_map": (i32, [dp, fp, sz, u64, i32, fp, fp, vp, C.POINTER(C.c_uint32)]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)

@@ -20,12 +20,28 @@ from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._lib import CameraUBO, RtError, Stats, check, lib
+from ._lib import RT_QUERY_ANY, CameraUBO, Hit, RtError, Stats, check, lib
 from .scene import BuiltCpuData, Camera
 
 REFERENCE_WIDTH = 1280          # VulkanEngine.java:45
 REFERENCE_HEIGHT = 720          # VulkanEngine.java:46
 REFERENCE_MAX_BOUNCES = 10      # compute_dynamic_ray.comp:44
+
+# rt_ray / rt_hit (include/rtamd.h) as numpy records, 32 bytes each
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("tri", "<i4"), ("normal", "<f4", (3,)), ("pos", "<f4", (3,))])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32
+
+
+def _rays(rays) -> np.ndarray:
+    """Rays as contiguous RAY_DTYPE records: from such records, or from
+    float32 (n, 8) rows (origin.xyz, t_max, dir.xyz, reserved)."""
+    r = np.asarray(rays)
+    if r.dtype == RAY_DTYPE:
+        return np.ascontiguousarray(r).reshape(-1)
+    if r.dtype.fields is None and r.ndim == 2 and r.shape[1] == 8:
+        return np.ascontiguousarray(r, dtype=np.float32).view(RAY_DTYPE).reshape(-1)
+    raise TypeError("rays must be RAY_DTYPE records or a float32 (n, 8) array")
 
 
 def _ubo(cam: Union[Camera, CameraUBO, bytes]) -> CameraUBO:
@@ -145,6 +161,60 @@ class Renderer:
                                           x0, y0, tile_w, tile_h, d_rgba, d_radiance, stream,
                                           C.byref(st) if st is not None else None))
         return st.as_dict() if st is not None else None
+
+    # --- ray queries (include/rtamd.h "queries") ---
+    def query_rays(self, rays, any_hit: bool = False, stats: bool = False):
+        """Closest hits (any_hit: any hit, RT_QUERY_ANY) of a batch of rays in
+        host memory (rt_query_rays): RAY_DTYPE records or float32 (n, 8) rows
+        in, HIT_DTYPE records out; with stats, (hits, stats dict)."""
+        r = _rays(rays)
+        hits = np.empty(len(r), dtype=HIT_DTYPE)
+        st = Stats() if stats else None
+        check(lib().rt_query_rays(self._ctx, r.ctypes.data, len(r), RT_QUERY_ANY if any_hit else 0,
+                                  hits.ctypes.data, C.byref(st) if st is not None else None))
+        return (hits, st.as_dict()) if st is not None else hits
+
+    def query_rays_device(self, d_rays: int, n_rays: int, d_hits: int, any_hit: bool = False,
+                          stream: Optional[int] = None, stats: bool = False):
+        """The same between device buffers (raw 16-byte aligned device
+        pointers) on a HIP stream handle (rt_query_rays_device); asynchronous
+        unless stats."""
+        st = Stats() if stats else None
+        check(lib().rt_query_rays_device(self._ctx, d_rays, n_rays, RT_QUERY_ANY if any_hit else 0, d_hits,
+                                         stream, C.byref(st) if st is not None else None))
+        return st.as_dict() if st is not None else None
+
+    def render_hits_device(self, camera, width: int, height: int, x0: int, y0: int, tile_w: int, tile_h: int,
+                           d_hits: int, stream: Optional[int] = None, any_hit: bool = False, stats: bool = False):
+        """Enqueue the first-hit buffer of a tile into a device buffer of
+        tile_h x tile_w rt_hit records (a raw 16-byte aligned device pointer)
+        on a HIP stream handle (rt_render_hits_device); asynchronous unless stats."""
+        st = Stats() if stats else None
+        check(lib().rt_render_hits_device(self._ctx, C.byref(_ubo(camera)), width, height, x0, y0, tile_w, tile_h,
+                                          RT_QUERY_ANY if any_hit else 0, d_hits, stream,
+                                          C.byref(st) if st is not None else None))
+        return st.as_dict() if st is not None else None
+
+    def render_hits(self, camera, width: int, height: int, tile: Optional[Tuple[int, int, int, int]] = None,
+                    any_hit: bool = False, stats: bool = False):
+        """The first-hit buffer of the frame render() draws: HIT_DTYPE records
+        [tile_h, tile_w] of the tile (x0, y0, tile_w, tile_h), default the
+        whole frame; with stats, (hits, stats dict)."""
+        import torch
+        x0, y0, tw, th = tile if tile is not None else (0, 0, width, height)
+        with torch.cuda.device(self.device_ids[0]):
+            d = torch.empty((max(th, 0), max(tw, 0), 8), dtype=torch.float32, device="cuda")
+            st = self.render_hits_device(camera, width, height, x0, y0, tw, th, d.data_ptr(),
+                                         torch.cuda.current_stream().cuda_stream, any_hit, stats)
+            hits = d.cpu().numpy().view(HIT_DTYPE)[..., 0]
+        return (hits, st) if stats else hits
+
+    def pick(self, camera, width: int, height: int, x: int, y: int) -> np.ndarray:
+        """The hit record (a HIT_DTYPE scalar) of pixel (x, y)'s primary ray
+        (rt_pick); rtamd.instance_of names its instance."""
+        h = Hit()
+        check(lib().rt_pick(self._ctx, C.byref(_ubo(camera)), width, height, x, y, C.byref(h)))
+        return np.frombuffer(bytes(h), dtype=HIT_DTYPE)[0]
 
 
 class PinnedFrame:

@@ -192,6 +192,9 @@ class BuiltCpuData:
     model_material_data: np.ndarray   # float32, 4 per flattened triangle
     flat_bvh_data: np.ndarray         # uint8, 48 per node
     triangle_count: int
+    # the input triangle (row of build_buffers' tri_verts) of every flattened
+    # triangle (rt_build_scene_map); None for buffers from elsewhere
+    flat_source: Optional[np.ndarray] = None
 
     @property
     def n_nodes(self) -> int:
@@ -234,9 +237,33 @@ def build_buffers(tri_verts: np.ndarray, tri_mats: np.ndarray, axis_seed: int = 
     v = np.empty(nf.value * 12, dtype=np.float32)
     m = np.empty(nf.value * 4, dtype=np.float32)
     b = np.empty(nn.value * 48, dtype=np.uint8)
-    check(L.rt_build_scene(_dptr(tri_verts), _fptr(tri_mats), n, axis_seed, n_threads,
-                           _fptr(v), _fptr(m), b.ctypes.data_as(C.c_void_p)))
-    return BuiltCpuData(v, m, b, nf.value)
+    src = np.empty(nf.value, dtype=np.uint32)
+    check(L.rt_build_scene_map(_dptr(tri_verts), _fptr(tri_mats), n, axis_seed, n_threads,
+                               _fptr(v), _fptr(m), b.ctypes.data_as(C.c_void_p),
+                               src.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return BuiltCpuData(v, m, b, nf.value, src)
+
+
+def instance_of(scene: Scene, built: BuiltCpuData, tri: int) -> ModelInstance:
+    """The ModelInstance a flattened triangle index (rt_hit.tri, Renderer.pick)
+    came from: built.flat_source names the input triangle, and the inputs are
+    the instances' meshes one after another in triangles_of's order (a model
+    that fails to load is skipped there and here)."""
+    if built.flat_source is None:
+        raise ValueError("these buffers carry no flat_source (not made by build_buffers)")
+    if not 0 <= tri < len(built.flat_source):
+        raise IndexError(f"triangle {tri} outside the scene's {len(built.flat_source)} flattened triangles")
+    src = int(built.flat_source[tri])
+    first = 0
+    for inst in scene.get_instances():
+        try:
+            n = len(inst.mesh())
+        except Exception:
+            continue
+        if src < first + n:
+            return inst
+        first += n
+    raise IndexError(f"input triangle {src} is past the scene's instances ({first} triangles)")
 
 
 class SceneBuilder:

@@ -43,7 +43,10 @@ extern "C" {
 /* Layout version of the structs below (rt_camera_ubo, rt_stats) and of the
  * calls' argument lists: bumped whenever one changes (round 4 moved
  * rt_stats.pixels to the end, SURVEY.md §8b's order).  A binding compiled
- * against another version must refuse the library (rt_abi_version). */
+ * against another version must refuse the library (rt_abi_version).  The ray
+ * queries (rt_ray, rt_hit, rt_query_*, rt_render_hits_device, rt_pick,
+ * rt_build_scene_map) were added at version 6 without a bump: no existing
+ * struct or argument list changed, so a version-6 binding still fits. */
 #define RT_ABI_VERSION 6
 
 typedef struct rt_ctx rt_ctx;
@@ -257,6 +260,67 @@ int rt_render_wait(rt_ctx* ctx, uint64_t ticket);
  * of blocking its thread. */
 int rt_render_poll(rt_ctx* ctx, uint64_t ticket, int* done);
 
+/* ---------------------------------------------------------------- queries -- */
+/* Ray queries: the walk of one segment of the shader's bounce loop
+ * (compute_dynamic_ray.comp:181-213), returning the hit instead of shading it.
+ *
+ * rt_ray: 32 bytes.  The walk runs with closest_t starting at t_max (:182 starts
+ * it at T_MAX) and T_MIN = 0.001 fixed (:42).  t_max >= T_MAX (1e4, :43) or NaN
+ * means T_MAX; t_max <= T_MIN cannot hit (hit_triangle keeps t > T_MIN and
+ * t < closest_t, :127).  hit_aabb (:88-103) and hit_triangle (:105-129)
+ * are the render kernels' arithmetic, bit for bit, and dir is used as given
+ * (it is not normalized).  reserved is ignored. */
+typedef struct rt_ray { float origin[3]; float t_max; float dir[3]; uint32_t reserved; } rt_ray;
+/* rt_hit: 32 bytes.  tri = the flattened triangle index of the reference's
+ * closest hit (the first found in preorder on a tie, :196-200), t its
+ * closest_t, normal = normalize(cross(e1, e2)) turned against dir (:124-125),
+ * pos = origin + dir * t, multiply then add, unfused (ray_at, :77-79).
+ * A miss: tri = -1, t = the effective t_max, zeros elsewhere.  A ray with a
+ * non-finite origin or direction component, or an all-zero direction, is not
+ * walked: tri = -2, t = 0, zeros elsewhere. */
+typedef struct rt_hit { float t; int32_t tri; float normal[3]; float pos[3]; } rt_hit;
+/* flags bit: a ray's walk may stop at the first hit that closest mode would
+ * keep (one not lying before its own box's t_enter).  tri >= 0 exactly when
+ * closest mode's is, and the record is a true intersection with T_MIN < t <
+ * t_max, not necessarily the closest.  For occlusion / shadow / AO rays.  A
+ * walk that cannot stop early (the cooperative tail) ignores it. */
+#define RT_QUERY_ANY 1
+
+/* n_rays (1 .. 2^26) rays from DEVICE memory to DEVICE hit records, both
+ * 16-byte aligned, on device 0 of ctx.  Ray i is walked by lane i % 64 of wave
+ * i / 64, in the caller's order: nothing is sorted, so coherent neighbours
+ * walk together.  Same stream / stats semantics as rt_render_tile_device
+ * (asynchronous unless stats is given).  stats: segments = rays walked,
+ * node_visits / tri_tests as the walk counts them (on the reference's tree:
+ * the reference DFS's counts), mat_reads = 0, pixels = n_rays.
+ * Exactness: on the accel tree (option accel 8 / 1) a ray whose
+ * dot(dir, dir) differs from 1 by more than 2^-10 is walked in the reference's
+ * order over the reference's records, since the accel walk's margins were
+ * audited on unit directions only; unit rays take the accel walk and its
+ * reference-order fallback, both from the ray's own t_max.  Scenes uploaded
+ * with accel_half / accel_wide are queried over their reference records.
+ * Queries see triangles only, whatever option "extensions" says (no spheres),
+ * and leave all render state alone: learned orders, graphs, async slots,
+ * accumulation sums, and "plain_kernels" (query kernels are not counted). */
+int rt_query_rays_device(rt_ctx* ctx, const rt_ray* d_rays, size_t n_rays, uint32_t flags,
+                         rt_hit* d_hits, void* stream, rt_stats* stats);
+/* The same from and to HOST memory; synchronous. */
+int rt_query_rays(rt_ctx* ctx, const rt_ray* rays, size_t n_rays, uint32_t flags,
+                  rt_hit* hits, rt_stats* stats);
+/* The first-hit buffer of the frame rt_render draws: the hit record of every
+ * pixel's own primary ray (seed, jitter and normalize exactly as :164-173) of
+ * the rectangle [x0, x0+tile_w) x [y0, y0+tile_h), row-major tile_h x tile_w
+ * records at DEVICE pointer d_hits (16-byte aligned).  Depth, normal and
+ * triangle-id buffers for a denoiser or an outline pass.  stats: pixels = the
+ * tile's pixels; otherwise as rt_query_rays_device. */
+int rt_render_hits_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height,
+                          int x0, int y0, int tile_w, int tile_h, uint32_t flags,
+                          rt_hit* d_hits, void* stream, rt_stats* stats);
+/* One pixel of the above into host memory, synchronous: the object under the
+ * cursor (rt_build_scene_map names the hit triangle's source). */
+int rt_pick(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int x, int y,
+            rt_hit* out_hit);
+
 /* Schedule options (no effect on results, which are identical for every
  * setting):
  *   "kernel"        0 only: the one kernel, one lane per pixel (the
@@ -466,7 +530,7 @@ int rt_render_poll(rt_ctx* ctx, uint64_t ticket, int* done);
  *                   on device 0 hold pad slots
  *   "plain_kernels" (rt_get_option only) production-build trace kernels enqueued
  *                   on device 0 so far (not counting, diagnostic or learning
- *                   launches): lets a profiler's kernel trace be cut at a
+ *                   launches, nor query launches): lets a profiler's kernel trace be cut at a
  *                   caller's region (bench.py, tools/rocprof_union.py)
  *   "hw_queues"     (rt_get_option only) GPU_MAX_HW_QUEUES as seen by rt_create
  *                   (4, HIP's default, when unset)
@@ -581,6 +645,15 @@ int rt_bvh_layout_size(size_t n_tris, size_t* n_nodes, size_t* n_flat_tris);
 int rt_build_scene(const double* tri_verts, const float* tri_mats, size_t n_tris,
                    uint64_t axis_seed, int n_threads,
                    float* out_vertices, float* out_materials, void* out_nodes);
+
+/* rt_build_scene with one more output: out_source[f] (n_flat entries) = the
+ * input triangle that flattened triangle f copies (the flattener writes a
+ * triangle twice when a range holds one, BVHBuilder.java:60-71), which turns
+ * rt_hit.tri back into the caller's own triangle.  NULL = rt_build_scene. */
+int rt_build_scene_map(const double* tri_verts, const float* tri_mats, size_t n_tris,
+                       uint64_t axis_seed, int n_threads,
+                       float* out_vertices, float* out_materials, void* out_nodes,
+                       uint32_t* out_source);
 
 /* Camera.recalculateViewport (Camera.java:44-68) in double, cast to float as
  * Vec3.store does (Vec3.java:132-136). */

@@ -120,6 +120,24 @@ JNIEXPORT jlong JNICALL Java_dev_demir_vulkan_engine_HipNative_getOption(JNIEnv*
     return (jlong)v;
 }
 
+/* void pick(long ctx, ByteBuffer ubo80, int w, int h, int x, int y, ByteBuffer outHit32)
+ * The hit record of pixel (x, y)'s primary ray (rtamd.h rt_pick, rt_hit: float t, int tri, float normal[3],
+ * float pos[3], native byte order) into a direct buffer of at least 32 bytes; tri < 0: nothing under the
+ * cursor.  Call it on the thread that owns ctx (the render thread): a context is single-thread-affine. */
+JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_pick(JNIEnv* env, jclass c, jlong ctx,
+        jobject ubo, jint w, jint h, jint x, jint y, jobject outHit) {
+    /* a heap (non-direct) buffer has capacity -1 */
+    if (!ubo || !outHit || (*env)->GetDirectBufferCapacity(env, ubo) < (jlong)sizeof(rt_camera_ubo) ||
+        (*env)->GetDirectBufferCapacity(env, outHit) < (jlong)sizeof(rt_hit)) {
+        jclass ex = (*env)->FindClass(env, "java/lang/RuntimeException");
+        if (ex) (*env)->ThrowNew(env, ex, "pick: need direct buffers of >= 80 bytes (camera UBO) and >= 32 bytes (hit)");
+        return;
+    }
+    int rc = rt_pick((rt_ctx*)(intptr_t)ctx, (const rt_camera_ubo*)(*env)->GetDirectBufferAddress(env, ubo),
+                     w, h, x, y, (rt_hit*)(*env)->GetDirectBufferAddress(env, outHit));
+    if (rc) throw_rt(env, rc);
+}
+
 JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_destroy(JNIEnv* env, jclass c, jlong ctx) {
     rt_destroy((rt_ctx*)(intptr_t)ctx);
 }

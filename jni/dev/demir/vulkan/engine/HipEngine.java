@@ -22,6 +22,8 @@ public class HipEngine implements Runnable {
     private final ConcurrentLinkedQueue<Camera> cameraQueue = new ConcurrentLinkedQueue<>();
     private final ConcurrentLinkedQueue<Boolean> skyToggleQueue = new ConcurrentLinkedQueue<>();
     private final ByteBuffer ubo = ByteBuffer.allocateDirect(80).order(ByteOrder.nativeOrder());
+    private final ByteBuffer hit = ByteBuffer.allocateDirect(32).order(ByteOrder.nativeOrder());   // rt_hit
+    private final ConcurrentLinkedQueue<Object[]> pickQueue = new ConcurrentLinkedQueue<>();
     private long ctx = 0;
     private boolean haveScene = false;
     private ByteBuffer[] slots = null;
@@ -44,6 +46,11 @@ public class HipEngine implements Runnable {
     public void submitScene(BuiltCpuData d) { sceneQueue.add(d); }
     public void submitCameraUpdate(Camera c) { cameraQueue.add(c); }
     public void submitSkyToggle(boolean on) { skyToggleQueue.add(on); }
+    /** The flattened triangle under pixel (x, y) of the current camera (negative: nothing), handed to onHit
+     *  on the render thread, which owns the context (rt_pick; a context is single-thread-affine). */
+    public void submitPick(int x, int y, java.util.function.IntConsumer onHit) {
+        pickQueue.add(new Object[]{x, y, onHit});
+    }
 
     @Override public void run() {
         try {
@@ -75,6 +82,11 @@ public class HipEngine implements Runnable {
                 currentCamera.getVertical().store(48, ubo);
                 ubo.putInt(64, currentCamera.getFrameCount());
                 ubo.putInt(68, isSkyEnabled);
+                Object[] pk;                                              // picks see the camera of this pass
+                while ((pk = pickQueue.poll()) != null) {
+                    HipNative.pick(ctx, ubo, WIDTH, HEIGHT, (Integer) pk[0], (Integer) pk[1], hit);
+                    ((java.util.function.IntConsumer) pk[2]).accept(hit.getInt(4));   // rt_hit.tri
+                }
                 // IN_FLIGHT (= the library's async_slots, default 4) frames in
                 // flight, each tracing on its own stream: the frames' traces
                 // overlap each other and every readback overlaps later traces.

@@ -18,4 +18,7 @@ final class HipNative {
     static native void uploadSpheres(long ctx, float[] spheres8n);   // extension (option "extensions" bit 8)
     static native void setOption(long ctx, String name, long value);
     static native long getOption(long ctx, String name);
+    /** rt_pick: the hit record of pixel (x, y) into outHit (direct, >= 32 bytes, native order: float t, int tri,
+     *  float normal[3], float pos[3]); tri < 0 = nothing hit.  On the thread that owns ctx. */
+    static native void pick(long ctx, ByteBuffer ubo80, int w, int h, int x, int y, ByteBuffer outHit);
 }
