@@ -147,6 +147,9 @@ struct TraceArgs {
     unsigned long long* diag;   // diagnostics: 8 words per wave, or null
     int      coop_lanes;        // finish a wave's walks cooperatively once at most
                                 //   this many lanes are still walking (0 = never)
+    int      solo_lanes;        // format-0 accel walk without the cooperative tail: once at most this many
+                                //   lanes of a wave are still walking, their walks are finished one ray at a
+                                //   time through the scalar cache (solo_walk, rt_trace.hip; 0 = never)
     int      ext;               // non-reference extensions, kExt* bits (0 = the reference)
     int      sky_enabled;       // CameraUBO.sky_enabled (@68), read only with kExtSkyToggle
     int      frame_count;       // CameraUBO.frame_count (@64), read only with kExtAccumulate

@@ -293,6 +293,7 @@ struct PerDevice {
     int          learning_tx = 0, learning_ty = 0, learning_frames = 0;   // its tiles (option xcd_order)
     int          last_heavy = 0;    // heavy tiles of the last launch (option "heavy_tiles_used", read only)
     int          last_heavy_px = 0; // heavy pixels of the last launch (option "heavy_pixels_used", read only)
+    int          last_solo = 0;     // solo_lanes of the last launch (option "solo_lanes_used", read only)
     // option graph: plain launches captured once per launch key into a HIP
     // graph and replayed (the heavy-tile fork / join becomes graph edges)
     struct Graph { std::vector<uint64_t> key; hipGraphExec_t exec; int kernels; };
@@ -372,6 +373,9 @@ struct rt_ctx {
     int  coop_lanes = -1;          // cooperative tail once <= this many lanes walk (0 = off); -1 (default) =
                                    //   1 on the reference-order walk, 0 on the accel walk (its walks are
                                    //   short: config 3 0.1253-0.1254 vs 0.1279-0.1288 ms, profiles/r05/r5b)
+    int  solo_lanes = -1;          // format-0 accel walk: once <= this many lanes of a wave walk, their walks
+                                   //   finish one ray at a time through the scalar cache (solo_walk, rt_trace.hip;
+                                   //   0 = off); -1 (default) = 1 there, 0 elsewhere
     int  ext = 0;                  // non-reference extensions (kExt* bits), off by default
     int  walk = 2;                 // 0 = node per step, 2 = node per step, software-pipelined over the
                                    //   compact records (fastest measured)
@@ -485,7 +489,7 @@ static int plan_order(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_ca
     // (the heavy-split options are part of the key: an order learned on the
     // device has no heavy tiles, one learned on the host does)
     std::vector<int> geo = {a.width, a.height, a.max_bounces, a.x0, a.y0, a.tw, a.th, a.band_h, a.band_stride,
-                            a.band_off, a.wave_tile, a.ext, a.coop_lanes, a.walk, ctx->learn_cost, ctx->order_split,
+                            a.band_off, a.wave_tile, a.ext, a.coop_lanes, a.solo_lanes, a.walk, ctx->learn_cost, ctx->order_split,
                             ctx->heavy_factor, concurrency(ctx), ctx->heavy_cap, ctx->heavy_pixel_factor,
                             a.n_frames, bands ? (int)bands->size() : -1, a.list_stride, ctx->order_frames,
                             ctx->heavy_stream, ctx->heavy_pixels, ctx->heavy_tiles, ctx->learn_device,
@@ -851,6 +855,13 @@ static int coop_window_of(const rt_ctx* ctx, const PerDevice& p) {
     return walk_bytes(p) > kWin32Bytes ? 32 : 64;
 }
 
+// Option solo_lanes: solo_walk reads format-0 accel records and takes the place
+// of a cooperative tail, in the kernels without extensions.
+static int solo_lanes_of(const rt_ctx* ctx, const DevScene& sc, int coop_lanes, int ext) {
+    if (!sc.n_layouts || sc.half || sc.wide || coop_lanes > 0 || ext) return 0;
+    return ctx->solo_lanes >= 0 ? ctx->solo_lanes : 1;
+}
+
 static int set_schedule(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_camera_ubo* cam,
                         const std::vector<int>* bands = nullptr) {
     a.wave_tile = wave_tile_of(ctx, p);
@@ -861,6 +872,7 @@ static int set_schedule(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_
     a.coop_win = coop_window_of(ctx, p);
     a.block_waves = ctx->block_waves;
     a.ext = ctx->ext;
+    a.solo_lanes = p.last_solo = solo_lanes_of(ctx, p.scene, a.coop_lanes, a.ext);
     a.scene.spheres = p.d_spheres;
     a.scene.n_spheres = (a.ext & kExtSpheres) ? p.n_spheres : 0;
     a.scene.oct_mask = ctx->accel_octants;
@@ -934,7 +946,7 @@ static std::vector<uint64_t> launch_key(const TraceArgs& a, hipStream_t s) {
             (uint64_t)a.width, (uint64_t)a.height, (uint64_t)a.max_bounces, (uint64_t)a.x0, (uint64_t)a.y0,
             (uint64_t)a.tw, (uint64_t)a.th, (uint64_t)a.band_h, (uint64_t)a.band_stride, (uint64_t)a.band_off,
             P(a.out_rgba), P(a.out_rad), (uint64_t)a.wave_tile,
-            (uint64_t)a.coop_lanes, (uint64_t)a.ext, (uint64_t)a.sky_enabled,
+            (uint64_t)a.coop_lanes, (uint64_t)a.solo_lanes, (uint64_t)a.ext, (uint64_t)a.sky_enabled,
             (uint64_t)a.frame_count, P(a.accum), (uint64_t)a.walk, (uint64_t)a.block_waves, P(a.tile_order),
             (uint64_t)a.heavy_tiles, (uint64_t)(a.aux_stream != nullptr), (uint64_t)a.heavy_fused, P(a.heavy_px),
             (uint64_t)a.n_heavy_px, P(a.tile_mask), (uint64_t)a.coop_walk, (uint64_t)a.coop_win,
@@ -1568,6 +1580,7 @@ static int run_query(rt_ctx* ctx, PerDevice& p, TraceArgs& a, uint64_t n, unsign
     a.diag = nullptr;
     a.coop_lanes = a.scene.n_layouts ? 0 : (ctx->coop_lanes >= 0 ? ctx->coop_lanes : 1);
     a.ext = 0;
+    a.solo_lanes = p.last_solo = solo_lanes_of(ctx, a.scene, a.coop_lanes, 0);
     a.sky_enabled = 1;
     a.frame_count = 0;
     a.accum = nullptr;
@@ -2272,6 +2285,7 @@ static constexpr Option one_of(const char* name, int rt_ctx::* field, int64_t a,
 }
 static const Option kOptions[] = {
     in_range("coop_lanes", &rt_ctx::coop_lanes, -1, 64),
+    in_range("solo_lanes", &rt_ctx::solo_lanes, -1, 64),
     in_range("extensions", &rt_ctx::ext, 0, 15),
     one_of("walk", &rt_ctx::walk, 0, 2),
     one_of("coop_window", &rt_ctx::coop_window, 0, 32, 64),
@@ -2352,6 +2366,7 @@ int rt_get_option(rt_ctx* ctx, const char* name, int64_t* value) {
     else if (is("leaf_align_used")) *value = p ? p->scene.padded : 0;
     else if (is("heavy_pixels_used")) *value = p ? p->last_heavy_px : 0;
     else if (is("heavy_tiles_used")) *value = p ? p->last_heavy : 0;
+    else if (is("solo_lanes_used")) *value = p ? p->last_solo : 0;
     else if (is("plain_kernels")) *value = p ? (int64_t)p->plain_kernels : 0;
     else if (is("hw_queues")) *value = ctx->hw_queues;
     // 1 when rt_render_async's slots cannot each have a hardware queue of their

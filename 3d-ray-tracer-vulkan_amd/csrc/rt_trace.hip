@@ -895,6 +895,8 @@ constexpr int kFeatAccel = 512;   // option accel: the accel records and rules, 
 constexpr int kFeatQuery = 16384; // query mode (launch_query): a lane's ray comes from
                                   //   TraceArgs::ray_in (or is its pixel's primary ray), is walked once
                                   //   from its own t_max, and its hit record is stored instead of shading
+constexpr int kFeatSolo = 32768;  // option solo_lanes (with kFeatAccel, format 0, no cooperative tail): the
+                                  //   last solo_lanes walks of a wave run in solo_walk's scalar loop
 constexpr unsigned kHeavyLaneMark = kLearnHeavyMark;   // rt_internal.h
 
 // A query's hit record (rtamd.h rt_hit): (t, tri, normal.xy), (normal.z, pos.xyz).
@@ -966,6 +968,79 @@ __device__ __forceinline__ void heavy_pixel(const TraceArgs& a, int f, int lx, i
     }
 }
 
+// ------------------------------------------------------------ solo walk --
+//
+// Option solo_lanes (kFeatSolo): the format-0 accel walk of ONE
+// ray, lane L's, from byte offset sb of the records to its layout's end se.
+// The lockstep loop pays a wave-level vector load per 16 B whatever its exec
+// mask, and 44% of config 3's lockstep steps serve a single lane
+// (tools/solo_model.py).  Here the record's offset is wave-uniform, so the
+// record comes through the scalar cache (constant address space: one 32-B
+// scalar load, and a leaf's other 32 B in the same round trip) and stays in
+// SGPRs, and the loop runs under scalar branches.  Exec stays full: every lane
+// runs the lockstep step's arithmetic (slab, accel_enter_lim, tri_test,
+// accel_take, in the same order) on its own ray against the SGPR record, and
+// only lane L's outcome is read, from bit L of a ballot; closest_t, the hit,
+// incons and lim are written under lane == L, so lane L's results are the
+// lockstep walk's bit for bit and no other lane's state changes.  The next
+// offset comes by scalar selects from the link word.  Counters are counted
+// once, by lane L; a diag build counts a solo step as one step of lane L.
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ u32x8 srec(const float4* __restrict__ walk, unsigned byte) {
+    typedef const __attribute__((address_space(4))) char* cbytes;
+    return *(const __attribute__((address_space(4))) u32x8*)((cbytes)walk + byte);
+}
+template <bool COUNT, bool DIAG, bool QRY>
+__device__ __forceinline__ void solo_walk(const float4* __restrict__ walk, int L, unsigned sb, unsigned se, bool sl,
+                                          bool any_hit, V3 o, V3 d, V3 inv, float& closest, int& hit, bool& incons,
+                                          float& lim, unsigned long long& c_node, unsigned long long& c_tri,
+                                          unsigned long long& d_iters) {
+    const bool me = (int)(threadIdx.x & 63) == L;
+    unsigned cn = 0, ct = 0, steps = 0;
+    for (;;) {
+        const u32x8 R = srec(walk, sb);
+        u32x8 T;
+        if (sl) T = srec(walk, sb + 32u);                        // a leaf's triangle: the slot after its box
+        const uint32_t aw = R[3], bw = R[7];
+        float te;
+        bool ind;
+        slab(make_float4(__uint_as_float(R[0]), __uint_as_float(R[1]), __uint_as_float(R[2]), 0.f),
+             make_float4(__uint_as_float(R[4]), __uint_as_float(R[5]), __uint_as_float(R[6]), 0.f), o, inv, te, ind);
+        const bool hb = ((__ballot(ind && accel_enter_lim(te, lim, aw)) >> L) & 1ull) != 0ull;
+        const unsigned tb = sb + (sl ? 64u : 32u);
+        sb = (hb || sl) ? tb : (aw << 5);
+        const bool nl = (hb && !sl) ? (int)bw < 0 : (int)aw < 0;
+        if (COUNT && hb && !sl) cn += 2;
+        if (DIAG) ++steps;
+        if (hb && sl) {                                              // hit_triangle (:196-200)
+            if (COUNT) ++ct;
+            float t;
+            const bool tv = tri_test(make_float4(__uint_as_float(bw), __uint_as_float(T[0]), __uint_as_float(T[1]), 0.f),
+                                     make_float4(__uint_as_float(T[2]), __uint_as_float(T[3]), __uint_as_float(T[4]), 0.f),
+                                     make_float4(__uint_as_float(T[5]), __uint_as_float(T[6]), __uint_as_float(T[7]), 0.f),
+                                     o, d, t) &&
+                            accel_take(t, (int)(aw & kTri), closest, hit);
+            if (((__ballot(tv) >> L) & 1ull) != 0ull && me) {
+                closest = t;
+                hit = (int)(aw & kTri);
+                incons = t < te;
+                lim = accel_lim(t);
+            }
+        }
+        sl = nl;
+        if (!(sb < se)) break;
+        // RT_QUERY_ANY: the first hit closest mode would keep as consistent ends the walk
+        if (QRY && any_hit && ((__ballot(hit >= 0 && !incons) >> L) & 1ull) != 0ull) break;
+    }
+    if (me) {
+        if (COUNT) {
+            c_node += cn;
+            c_tri += ct;
+        }
+        if (DIAG) d_iters += steps;
+    }
+}
+
 // Occupancy floor for trace_simple (waves per SIMD).  Unconstrained, the
 // walk-2 build takes ~70 VGPRs (7 waves).  One frame at a time more waves did
 // not pay (round 1); with frames in flight the device is throughput-bound and
@@ -1000,6 +1075,10 @@ void trace_simple(TraceArgs a) {
     constexpr bool PAD = !ACC && ((FEAT & kFeatPad) || (FEAT & (kFeatExt | kFeatFrontier)) || !(FEAT & kFeatCoopTail));
     constexpr bool Q1 = (FEAT & kFeatQ1) != 0, Q2 = (FEAT & kFeatQ2) != 0;
     constexpr bool QRY = (FEAT & kFeatQuery) != 0;
+    // the solo walk: format-0 accel records, no cooperative tail, no extensions
+    constexpr bool SOLO = (FEAT & kFeatSolo) != 0;
+    static_assert(!SOLO || (ACC && !HALF && !WIDE && WALK == 2 && !(FEAT & (kFeatCoopTail | kFeatExt))),
+                  "kFeatSolo goes with the format-0 accel walk alone");
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     // frontier_walk's per-wave frontiers (kFCap entries per wave; dynamic LDS,
@@ -1241,6 +1320,11 @@ void trace_simple(TraceArgs a) {
                 WIDE ? (int)((unsigned)(a.scene.end2 + 1) * 64u)
                      : HALF ? (int)((unsigned)(a.scene.end2 + 4) * 16u) : (int)((unsigned)(a.scene.end2 + 2) * 32u),
                 0x00020000);
+            // kFeatSolo: the lanes that walk at all; a bounce that starts with at
+            // most solo_lanes of them never enters the lockstep loop (and issues
+            // no vector load for it)
+            const bool walk0 = walking;
+            if (SOLO && __popcll(__ballot(walking)) <= a.solo_lanes) walking = false;
             if (WIDE) {
                 // no prefetch: a step reads its record at the top
             } else if (HALF && walking) {
@@ -1391,6 +1475,23 @@ void trace_simple(TraceArgs a) {
                 }
                 if (WALK == 0 || HALF) walking = n < (ACC ? lend : wend);
                 if ((FEAT & kFeatCoopTail) && __popcll(__ballot(walking)) <= coop_lanes) break;
+                // kFeatSolo: the last solo_lanes walks leave the loop by its own
+                // condition (a break here cost the loop a second exit and ~25
+                // scalar instructions per step)
+                if (SOLO) walking = walking && __popcll(__ballot(walking)) > a.solo_lanes;
+            }
+            if (SOLO) {
+                // Every lane is here.  The walks still open (inside their layout,
+                // not ended by an any-hit query), one ray at a time.
+                uint64_t rem = __ballot(walk0 && nb < lend_b && !(QRY && a.any_hit && hit >= 0 && !incons));
+                while (rem != 0) {
+                    const int L = __ffsll((long long)rem) - 1;
+                    rem &= rem - 1;
+                    solo_walk<COUNT, DIAG, QRY>(wr, L, (unsigned)lane_i((int)nb, L), (unsigned)lane_i((int)lend_b, L),
+                                                lane_i((int)nleaf, L) != 0, QRY && a.any_hit, o, d, inv, closest, hit,
+                                                incons, lim, c_node, c_tri, d_iters);
+                }
+                walking = false;
             }
             if (BYTES) n = (int)(nb >> 5);
             __builtin_amdgcn_s_setprio(0);
@@ -1660,7 +1761,11 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels) {
             // split launch: kernel 1 to bounce split_bounce,
             // the scan of its per-wave counts, kernel 2 for the rest
             ao.q_waves = (int)(grid.x * grid.y) * bw;
-            hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ1, 2>), grid, block, 0, stream, ao);
+            if (a.solo_lanes > 0)
+                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ1 | kFeatSolo, 2>), grid, block, 0,
+                                   stream, ao);
+            else
+                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ1, 2>), grid, block, 0, stream, ao);
             size_t tb = a.q_temp_bytes;
             const hipError_t se = rocprim::exclusive_scan(a.q_temp, tb, a.q_count, a.q_prefix, 0u,
                                                           (size_t)ao.q_waves, rocprim::plus<unsigned>(), stream);
@@ -1669,8 +1774,12 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels) {
             a2.tile_order = nullptr;
             a2.split_n = 0;
             a2.block_waves = 1;
-            hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ2, 2>), dim3(a.q_grid), dim3(64), 0,
-                               stream, a2);
+            if (a.solo_lanes > 0)
+                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ2 | kFeatSolo, 2>), dim3(a.q_grid),
+                                   dim3(64), 0, stream, a2);
+            else
+                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ2, 2>), dim3(a.q_grid), dim3(64), 0,
+                                   stream, a2);
             if (kernels) *kernels = 2;                          // the frame kernels (q_scan aside)
             return hipGetLastError();
         }
@@ -1699,7 +1808,11 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels) {
                 if (a.coop_win == 32) RT_SIMPLE(kFeatCoopTail | kFeatAccel | kFeatWin32, 2)
                 else RT_SIMPLE(kFeatCoopTail | kFeatAccel, 2)
                 break;
-            case 0: RT_SIMPLE(kFeatAccel, 2) break;
+            case 0:
+                // (solo_lanes > 0 only where set_schedule allows it: format 0, no tail, no extensions)
+                if (a.solo_lanes > 0) RT_SIMPLE(kFeatAccel | kFeatSolo, 2)
+                else RT_SIMPLE(kFeatAccel, 2)
+                break;
             default: RT_SIMPLE(kFeatCoopTail | kFeatExt | kFeatAccel, 2) break;
         }
     } else if (a.walk == 2) {
@@ -1755,7 +1868,11 @@ hipError_t launch_query(const TraceArgs& a, hipStream_t stream) {
     ao.ext = 0;
     const dim3 grid((unsigned)ao.tiles_x * (unsigned)ao.tiles_y), block(64);
     constexpr int FA = kFeatAccel | kFeatQuery, FR = kFeatCoopTail | kFeatPad | kFeatQuery;
-    if (a.scene.n_layouts > 0) {
+    constexpr int FS = FA | kFeatSolo;
+    if (a.scene.n_layouts > 0 && a.solo_lanes > 0) {
+        if (a.counters) hipLaunchKernelGGL((trace_simple<true, false, FS, 2>), grid, block, 0, stream, ao);
+        else hipLaunchKernelGGL((trace_simple<false, false, FS, 2>), grid, block, 0, stream, ao);
+    } else if (a.scene.n_layouts > 0) {
         if (a.counters) hipLaunchKernelGGL((trace_simple<true, false, FA, 2>), grid, block, 0, stream, ao);
         else hipLaunchKernelGGL((trace_simple<false, false, FA, 2>), grid, block, 0, stream, ao);
     } else {

@@ -82,7 +82,7 @@ class Renderer:
 
     def set_option(self, name: str, value: int) -> None:
         """Schedule options (rt_set_option; the list is in include/rtamd.h):
-        "walk", "coop_lanes", "heavy_first", "concurrent_launches", ...
+        "walk", "coop_lanes", "solo_lanes", "heavy_first", "concurrent_launches", ...
         Results do not depend on them."""
         check(lib().rt_set_option(self._ctx, name.encode(), int(value)))
 

@@ -400,6 +400,16 @@ int rt_pick(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int x,
  *                   the whole wave finishes their walks one ray at a time
  *                   (0..64; 0 = off; -1, the default = 1 on the reference's
  *                   tree, 0 on the accel tree)
+ *   "solo_lanes"    the accel tree's format-0 walk (accel 1 / 8 without
+ *                   accel_half / accel_wide, no cooperative tail, no
+ *                   extensions): once at most this many lanes of a wave are
+ *                   still walking, their walks finish one ray at a time with
+ *                   the records read through the scalar cache instead of by
+ *                   wave-level vector loads (0..64; 0 = off; -1, the default =
+ *                   1 there and 0 everywhere else).  Frames, hit records and
+ *                   work counters do not change
+ *   "solo_lanes_used" (rt_get_option only) the solo_lanes the last launch on
+ *                   device 0 ran with (0 where the option does not apply)
  *   "coop_walk"     cooperative walks (the coop tail): 0 = 64-node preorder
  *                   windows (default), 1 = preorder frontier (up to 64 live
  *                   subtrees expanded per round trip)
