@@ -265,4 +265,20 @@ void set_error(const char* fmt, ...);
 hipError_t wire_pack(const void* rgba, void* rgb, size_t n_px, hipStream_t s);
 hipError_t wire_unpack(const void* rgb, void* rgba, size_t n_px, hipStream_t s);
 
+// rt_denoise.hip: the a-trous filter's passes (rtamd.h rt_denoise_device,
+// DESIGN.md §4g), enqueued on `stream`; validated arguments, nothing allocated.
+struct DenoiseArgs {
+    int           width, height;
+    const float*  radiance;     // the render's radiance, 3 floats per pixel
+    const float4* hits;         // rt_hit records, 2 float4 per pixel
+    float4*       workspace;    // 2 x width x height float4
+    uchar4*       out_rgba;     // nullable
+    float*        out_rad;      // nullable
+    int           iterations, normal_power_log2;
+    float         sigma_depth, inv_sigma_color;   // 1.0f / sigma_color, computed in float on the host
+    int           form;         // option denoise_kernel: 0 = the measured choice per step, 1 = plain, 2 = tiled
+    int           only_pass;    // option denoise_pass: -1 = every pass, i = pass i alone (timing)
+};
+hipError_t launch_denoise(const DenoiseArgs& d, hipStream_t stream);
+
 }  // namespace rtamd

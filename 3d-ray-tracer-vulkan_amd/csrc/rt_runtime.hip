@@ -312,6 +312,10 @@ struct PerDevice {
     char*        d_query = nullptr;
     size_t       query_cap = 0;      // bytes
     int          ref_root_leaf = 0;
+    // rt_render_denoised: one allocation holding the frame's radiance, hit
+    // records, filter workspace and filtered outputs, grown on demand
+    char*        d_denoise = nullptr;
+    size_t       denoise_cap = 0;    // bytes
 };
 
 static constexpr size_t kMaxOrders = 16;
@@ -413,6 +417,9 @@ struct rt_ctx {
     int  accel_half = 0;           // at the next upload: accel records in format 1, the internal boxes in
                                    //   half precision (accel_build.h)
     int  accel_wide = 0;           // at the next upload: the 4-wide tree, format 2 (overrides accel_half)
+    int  denoise_kernel = 0;       // rt_denoise_device: 0 = per step size the form measured faster, 1 = the
+                                   //   plain form, 2 = the tiled form (rt_denoise.hip; same results)
+    int  denoise_pass = -1;        // rt_denoise_device: i >= 0 = enqueue pass i alone (tools/denoise_bench.py)
     int  split_bounce = 0;         // accel walk: paths alive at this bounce finish in a second kernel
                                    //   (0 = one kernel)
     // At the next upload: 0 = the reference's tree and order; 1 / 8 = the
@@ -1216,6 +1223,7 @@ int rt_destroy(rt_ctx* ctx) {
         if (p.d_accum) (void)hipFree(p.d_accum);
         if (p.d_spheres) (void)hipFree(p.d_spheres);
         if (p.d_query) (void)hipFree(p.d_query);
+        if (p.d_denoise) (void)hipFree(p.d_denoise);
         if (p.d_rgba) (void)hipFree(p.d_rgba);
         if (p.d_rad) (void)hipFree(p.d_rad);
         if (p.ev0) (void)hipEventDestroy(p.ev0);
@@ -1715,6 +1723,157 @@ int rt_pick(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int x,
                                nullptr);
     if (rc) return rc;
     RT_HIP_CHECK(hipMemcpyAsync(out_hit, p.d_query, sizeof(rt_hit), hipMemcpyDeviceToHost, p.stream));
+    RT_HIP_CHECK(hipStreamSynchronize(p.stream));
+    return RT_OK;
+}
+
+// ------------------------------------------------------------------ denoise --
+// The filter reads and writes the caller's buffers only: like a query it
+// touches no render state, and its kernels are not counted in plain_kernels.
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+static int check_denoise_params(const rt_denoise_params* q, const char* fn) {
+    if (q->iterations < 1 || q->iterations > 6 || q->normal_power_log2 < 0 || q->normal_power_log2 > 10) {
+        set_error("%s: iterations must be in [1, 6] and normal_power_log2 in [0, 10], got %d and %d", fn,
+                  q->iterations, q->normal_power_log2);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite(q->sigma_depth) || !std::isfinite(q->sigma_color) || !(q->sigma_depth > 0.0f) ||
+        !(q->sigma_color > 0.0f)) {
+        set_error("%s: sigma_depth and sigma_color must be finite and > 0, got %g and %g", fn,
+                  (double)q->sigma_depth, (double)q->sigma_color);
+        return RT_ERR_INVALID_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radiance, const rt_hit* d_hits,
+                      const rt_denoise_params* params, void* d_workspace, void* d_out_rgba, float* d_out_radiance,
+                      void* stream, double* ms) {
+    if (!ctx || !d_radiance || !d_hits || !d_workspace) {
+        set_error("rt_denoise_device: null context or buffer");
+        return RT_ERR_INVALID_ARG;
+    }
+    if (!d_out_rgba && !d_out_radiance) { set_error("rt_denoise_device: both outputs are null"); return RT_ERR_INVALID_ARG; }
+    const size_t ws_bytes = rt_denoise_workspace_bytes(width, height);
+    if (ws_bytes == 0) { set_error("rt_denoise_device: bad frame size %dx%d", width, height); return RT_ERR_INVALID_ARG; }
+    rt_denoise_params q;
+    rt_denoise_default_params(&q);
+    if (params) q = *params;
+    if (int rc = check_denoise_params(&q, "rt_denoise_device")) return rc;
+    if ((((uintptr_t)d_hits | (uintptr_t)d_workspace) & 15u) ||
+        (((uintptr_t)d_radiance | (uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
+        set_error("rt_denoise_device: d_hits and d_workspace must be 16-byte aligned, the other buffers 4-byte");
+        return RT_ERR_INVALID_ARG;
+    }
+    const size_t px = (size_t)width * (size_t)height;
+    const struct { const void* p; size_t n; const char* name; } in[3] = {
+        {d_radiance, px * 12, "d_radiance"}, {d_hits, px * 32, "d_hits"}, {d_workspace, ws_bytes, "d_workspace"}};
+    const struct { const void* p; size_t n; const char* name; } out[2] = {
+        {d_out_rgba, px * 4, "d_out_rgba"}, {d_out_radiance, px * 12, "d_out_radiance"}};
+    for (const auto& o : out) {
+        if (!o.p) continue;
+        for (const auto& i : in)
+            if (ranges_overlap(o.p, o.n, i.p, i.n)) {
+                set_error("rt_denoise_device: %s overlaps %s", o.name, i.name);
+                return RT_ERR_INVALID_ARG;
+            }
+    }
+    if (d_out_rgba && d_out_radiance && ranges_overlap(out[0].p, out[0].n, out[1].p, out[1].n)) {
+        set_error("rt_denoise_device: d_out_rgba overlaps d_out_radiance");
+        return RT_ERR_INVALID_ARG;
+    }
+    for (int k = 0; k < 2; ++k)
+        if (ranges_overlap(in[2].p, in[2].n, in[k].p, in[k].n)) {
+            set_error("rt_denoise_device: d_workspace overlaps %s", in[k].name);
+            return RT_ERR_INVALID_ARG;
+        }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DenoiseArgs d;
+    d.width = width; d.height = height;
+    d.radiance = d_radiance;
+    d.hits = reinterpret_cast<const float4*>(d_hits);
+    d.workspace = static_cast<float4*>(d_workspace);
+    d.out_rgba = static_cast<uchar4*>(d_out_rgba);
+    d.out_rad = d_out_radiance;
+    d.iterations = q.iterations;
+    d.normal_power_log2 = q.normal_power_log2;
+    d.sigma_depth = q.sigma_depth;
+    d.inv_sigma_color = 1.0f / q.sigma_color;
+    d.form = ctx->denoise_kernel;
+    d.only_pass = ctx->denoise_pass < q.iterations ? ctx->denoise_pass : -1;
+    if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
+    RT_HIP_CHECK(launch_denoise(d, s));
+    if (ms) {
+        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
+        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
+        float t = 0.0f;
+        RT_HIP_CHECK(hipEventElapsedTime(&t, p.ev0, p.ev1));
+        *ms = (double)t;
+    }
+    return RT_OK;
+}
+
+int rt_render_denoised(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                       const rt_denoise_params* params, uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
+    int rc = check_render_args(ctx, cam, width, height, max_bounces, "rt_render_denoised");
+    if (rc) return rc;
+    if (!out_rgba) { set_error("rt_render_denoised: out_rgba is required"); return RT_ERR_INVALID_ARG; }
+    if (ctx->dev.size() != 1) {
+        set_error("rt_render_denoised: the context has %zu devices; the filter runs on whole frames of one device",
+                  ctx->dev.size());
+        return RT_ERR_INVALID_ARG;
+    }
+    PerDevice& p = ctx->dev[0];
+    if ((ctx->ext & kExtSpheres) && p.n_spheres > 0) {
+        set_error("rt_render_denoised: spheres are active (extensions bit 8); the hit buffer sees triangles only");
+        return RT_ERR_INVALID_ARG;
+    }
+    if (params)
+        if (int rq = check_denoise_params(params, "rt_render_denoised")) return rq;
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    // radiance (12 B), hit records (32 B), workspace (32 B), RGBA8 (4 B), filtered radiance (12 B) per
+    // pixel, each part on a 256-byte boundary
+    const size_t px = (size_t)width * (size_t)height;
+    const auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t o_hits = up(px * 12), o_ws = o_hits + up(px * 32), o_rgba = o_ws + up(px * 32),
+                 o_rad = o_rgba + up(px * 4), total = o_rad + up(px * 12);
+    if (total > p.denoise_cap) {
+        if (p.d_denoise) {
+            RT_HIP_CHECK(hipStreamSynchronize(p.stream));   // (the call is synchronous: nothing in flight)
+            (void)hipFree(p.d_denoise);
+        }
+        p.d_denoise = nullptr;
+        p.denoise_cap = 0;
+        const hipError_t e = hipMalloc(&p.d_denoise, total);
+        if (e != hipSuccess) {
+            set_error("rt_render_denoised: %zu bytes of frame buffers: %s", total, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+        }
+        p.denoise_cap = total;
+    }
+    float* d_rad = reinterpret_cast<float*>(p.d_denoise);
+    rt_hit* d_hits = reinterpret_cast<rt_hit*>(p.d_denoise + o_hits);
+    // the ordinary render of the frame, as a caller of rt_render_tile_device would enqueue it
+    rc = rt_render_tile_device(ctx, cam, width, height, max_bounces, 0, 0, width, height, nullptr, d_rad, p.stream,
+                               stats);
+    if (rc) return rc;
+    rc = rt_render_hits_device(ctx, cam, width, height, 0, 0, width, height, 0, d_hits, p.stream, nullptr);
+    if (rc) return rc;
+    double dn_ms = 0.0;
+    rc = rt_denoise_device(ctx, width, height, d_rad, d_hits, params, p.d_denoise + o_ws, p.d_denoise + o_rgba,
+                           out_radiance ? reinterpret_cast<float*>(p.d_denoise + o_rad) : nullptr, p.stream,
+                           stats ? &dn_ms : nullptr);
+    if (rc) return rc;
+    if (stats) stats->ms += dn_ms;
+    RT_HIP_CHECK(hipMemcpyAsync(out_rgba, p.d_denoise + o_rgba, px * 4, hipMemcpyDeviceToHost, p.stream));
+    if (out_radiance)
+        RT_HIP_CHECK(hipMemcpyAsync(out_radiance, p.d_denoise + o_rad, px * 12, hipMemcpyDeviceToHost, p.stream));
     RT_HIP_CHECK(hipStreamSynchronize(p.stream));
     return RT_OK;
 }
@@ -2317,6 +2476,8 @@ static const Option kOptions[] = {
     one_of("graph", &rt_ctx::graph, 0, 1),
     one_of("diag", &rt_ctx::diag, 0, 1),
     in_range("wave_tile", &rt_ctx::wave_tile, -1, 3),
+    in_range("denoise_kernel", &rt_ctx::denoise_kernel, 0, 2),
+    in_range("denoise_pass", &rt_ctx::denoise_pass, -1, 5),
 };
 
 static const Option* find_option(const char* name) {

@@ -39,13 +39,14 @@ EXPORTED = (
     "rt_render_poll", "rt_accel_records", "rt_abi_version", "rt_pack_rgb", "rt_unpack_rgb",
     "rt_build_id", "rt_render_batch_rect_device", "rt_render_batch_runs_device",
     "rt_query_rays_device", "rt_query_rays", "rt_render_hits_device", "rt_pick", "rt_build_scene_map",
+    "rt_denoise_default_params", "rt_denoise_workspace_bytes", "rt_denoise_device", "rt_render_denoised",
 )
 
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
 # "src=" field is the first 16 hex digits of SHA-256 over them concatenated.
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
-                 "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h", "csrc/accel_build.h",
-                 "../include/rtamd.h")
+                 "csrc/rt_denoise.hip", "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h",
+                 "csrc/accel_build.h", "../include/rtamd.h")
 
 
 def source_hash() -> str:
@@ -117,10 +118,19 @@ class Hit(C.Structure):                 # rt_hit
     _fields_ = [("t", C.c_float), ("tri", C.c_int32), ("normal", C.c_float * 3), ("pos", C.c_float * 3)]
 
 
+class DenoiseParams(C.Structure):       # rt_denoise_params; the defaults are rt_denoise_default_params's
+    _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("sigma_depth", C.c_float),
+                ("sigma_color", C.c_float)]
+
+    def __init__(self, iterations: int = 4, normal_power_log2: int = 7, sigma_depth: float = 0.005,
+                 sigma_color: float = 0.5):
+        super().__init__(iterations, normal_power_log2, sigma_depth, sigma_color)
+
+
 RT_QUERY_ANY = 1
 
 assert C.sizeof(CameraUBO) == 80
-assert C.sizeof(Ray) == 32 and C.sizeof(Hit) == 32
+assert C.sizeof(Ray) == 32 and C.sizeof(Hit) == 32 and C.sizeof(DenoiseParams) == 16
 
 _lock = threading.Lock()
 _lib = None
@@ -196,6 +206,11 @@ def lib() -> C.CDLL:
                                                 vp, vp, C.POINTER(Stats)]),
                 "rt_pick": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, i32, C.POINTER(Hit)]),
                 "rt_build_scene_map": (i32, [dp, fp, sz, u64, i32, fp, fp, vp, C.POINTER(C.c_uint32)]),
+                "rt_denoise_default_params": (None, [C.POINTER(DenoiseParams)]),
+                "rt_denoise_workspace_bytes": (sz, [i32, i32]),
+                "rt_denoise_device": (i32, [vp, i32, i32, vp, vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, dp]),
+                "rt_render_denoised": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, C.POINTER(DenoiseParams), vp, vp,
+                                             C.POINTER(Stats)]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)

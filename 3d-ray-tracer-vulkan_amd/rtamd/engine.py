@@ -20,7 +20,7 @@ from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._lib import RT_QUERY_ANY, CameraUBO, Hit, RtError, Stats, check, lib
+from ._lib import RT_QUERY_ANY, CameraUBO, DenoiseParams, Hit, RtError, Stats, check, lib
 from .scene import BuiltCpuData, Camera
 
 REFERENCE_WIDTH = 1280          # VulkanEngine.java:45
@@ -216,6 +216,57 @@ class Renderer:
         check(lib().rt_pick(self._ctx, C.byref(_ubo(camera)), width, height, x, y, C.byref(h)))
         return np.frombuffer(bytes(h), dtype=HIT_DTYPE)[0]
 
+    # --- denoiser (include/rtamd.h "denoise") ---
+    @staticmethod
+    def denoise_workspace_bytes(width: int, height: int) -> int:
+        """Bytes of denoise_device's workspace (rt_denoise_workspace_bytes)."""
+        return lib().rt_denoise_workspace_bytes(width, height)
+
+    def denoise_device(self, width: int, height: int, d_radiance: int, d_hits: int, d_workspace: int,
+                       d_out_rgba: Optional[int] = None, d_out_radiance: Optional[int] = None,
+                       params: Optional[DenoiseParams] = None, stream: Optional[int] = None, ms: bool = False):
+        """Enqueue the edge-avoiding filter of one whole frame between device
+        buffers (raw device pointers; rt_denoise_device) on a HIP stream
+        handle; asynchronous unless ms, which waits and returns the passes'
+        device time in milliseconds."""
+        t = C.c_double() if ms else None
+        check(lib().rt_denoise_device(self._ctx, width, height, d_radiance, d_hits,
+                                      C.byref(params) if params is not None else None, d_workspace, d_out_rgba,
+                                      d_out_radiance, stream, C.byref(t) if t is not None else None))
+        return t.value if t is not None else None
+
+    def denoise(self, radiance, hits, params: Optional[DenoiseParams] = None):
+        """The filter on host arrays: radiance float32 [H, W, 3] (render()'s)
+        and HIT_DTYPE records [H, W] (render_hits()'s) in, (rgba uint8
+        [H, W, 4], radiance float32 [H, W, 3]) out."""
+        import torch
+        rad = np.ascontiguousarray(radiance, dtype=np.float32)
+        h, w = rad.shape[:2]
+        hit = np.ascontiguousarray(hits, dtype=HIT_DTYPE).reshape(h, w)
+        with torch.cuda.device(self.device_ids[0]):
+            d_rad = torch.from_numpy(rad).cuda()
+            d_hit = torch.from_numpy(hit.view(np.float32).reshape(h, w, 8)).cuda()
+            d_ws = torch.empty((2, h, w, 4), dtype=torch.float32, device="cuda")
+            o_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda")
+            o_rad = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+            self.denoise_device(w, h, d_rad.data_ptr(), d_hit.data_ptr(), d_ws.data_ptr(), o_rgba.data_ptr(),
+                                o_rad.data_ptr(), params, torch.cuda.current_stream().cuda_stream)
+            return o_rgba.cpu().numpy(), o_rad.cpu().numpy()
+
+    def render_denoised(self, camera, width: int, height: int, max_bounces: int = REFERENCE_MAX_BOUNCES,
+                        params: Optional[DenoiseParams] = None, radiance: bool = False, stats: bool = False):
+        """render() followed by the filter (rt_render_denoised): (rgba, radiance
+        or None, stats dict or None); stats are the render's, ms with the
+        filter's time added.  One device, no active spheres."""
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        rad = np.empty((height, width, 3), dtype=np.float32) if radiance else None
+        st = Stats() if stats else None
+        check(lib().rt_render_denoised(self._ctx, C.byref(_ubo(camera)), width, height, max_bounces,
+                                       C.byref(params) if params is not None else None, rgba.ctypes.data,
+                                       rad.ctypes.data if rad is not None else None,
+                                       C.byref(st) if st is not None else None))
+        return rgba, rad, (st.as_dict() if st is not None else None)
+
 
 class PinnedFrame:
     """An RGBA8 frame in pinned host memory (rt_host_alloc), as a numpy view."""
@@ -273,13 +324,15 @@ class HipEngine:
     def __init__(self, frame_queue: AtomicReference, width: int = REFERENCE_WIDTH,
                  height: int = REFERENCE_HEIGHT, max_bounces: int = REFERENCE_MAX_BOUNCES,
                  device_ids: Sequence[int] = (0,), collect_stats: bool = False, pipelined: bool = True,
-                 inflight: int = 4):
+                 inflight: int = 4, denoise: Optional[DenoiseParams] = None):
         self.frame_queue = frame_queue
         # pipelined: `inflight` frames in flight (rt_render_async, one slot and
         # trace stream each), so the frames' traces overlap each other and
         # their readbacks; the reference waits for each frame
         # (VulkanEngine.java:410-429).  Stats need the synchronous path.
-        self.pipelined = pipelined and not collect_stats
+        # denoise: every frame goes through render_denoised, which is synchronous.
+        self.denoise = denoise
+        self.pipelined = pipelined and not collect_stats and denoise is None
         self.inflight = max(1, min(8, int(inflight)))
         self.width, self.height, self.max_bounces = width, height, max_bounces
         self.device_ids = tuple(device_ids)
@@ -345,8 +398,12 @@ class HipEngine:
                 ubo = CameraUBO.from_buffer_copy(bytes(camera.ubo))
                 ubo.sky_enabled = self.is_sky_enabled        # written, ignored by the shader
                 if not self.pipelined:
-                    rgba, _, st = renderer.render(ubo, self.width, self.height, self.max_bounces,
-                                                  stats=self.collect_stats)
+                    if self.denoise is not None:
+                        rgba, _, st = renderer.render_denoised(ubo, self.width, self.height, self.max_bounces,
+                                                               self.denoise, stats=self.collect_stats)
+                    else:
+                        rgba, _, st = renderer.render(ubo, self.width, self.height, self.max_bounces,
+                                                      stats=self.collect_stats)
                     self._publish(FrameData(rgba, st))
                     continue
                 if slots is None:

@@ -321,6 +321,58 @@ int rt_render_hits_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int 
 int rt_pick(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int x, int y,
             rt_hit* out_hit);
 
+/* ---------------------------------------------------------------- denoise -- */
+/* NON-REFERENCE (the reference shows its 1-sample frames as they are): an
+ * edge-avoiding a-trous wavelet filter for 1-sample frames, guided by the
+ * first-hit buffer of rt_render_hits_device.  `iterations` passes of a 5x5 B3
+ * spline (3/8, 1/4, 1/16 by |offset|) with step 2^i in pass i, on the linear
+ * colour (radiance squared); a tap's weight is the spline's times
+ * max(0, n_p . n_q)^(2^normal_power_log2) / ((1 + x^2) (1 + y^2)), x = the
+ * tap's distance from the centre pixel's tangent plane / (sigma_depth * t_p),
+ * y = the luminance difference * 2^i / sigma_color.  Pixels and taps without a
+ * hit (tri < 0) take no part: such a pixel keeps its colour bit for bit, so
+ * does one whose weights sum to zero or NaN.  The contract, operation by
+ * operation in IEEE binary32, is DESIGN.md §4g (tests/denoise_ref.py restates
+ * it in numpy, bit for bit).  Added at ABI version 6 without a bump, as the
+ * queries were: no existing struct or argument list changed. */
+typedef struct rt_denoise_params { int32_t iterations;        /* 1..6 */
+                                   int32_t normal_power_log2; /* 0..10 */
+                                   float sigma_depth, sigma_color; /* finite, > 0 */ } rt_denoise_params; /* 16 B */
+/* The defaults: 4 passes, normal_power_log2 7, sigma_depth 0.005, sigma_color 0.5. */
+void   rt_denoise_default_params(rt_denoise_params* out);
+/* Bytes of the filter's scratch for a width x height frame: 2 * width * height
+ * * 16 (0 for a bad size).  Pure host code. */
+size_t rt_denoise_workspace_bytes(int width, int height);
+/* Filters one whole width x height frame on device 0 of ctx, between DEVICE
+ * buffers: d_radiance (width*height*3 floats, the render's sqrt'd colour) and
+ * d_hits (width*height rt_hit records, 16-byte aligned) in, d_out_rgba
+ * (width*height*4 bytes, RGBA8 as the render quantises it, alpha 255) and / or
+ * d_out_radiance (width*height*3 floats) out; at least one output.
+ * d_workspace: rt_denoise_workspace_bytes bytes, 16-byte aligned, left as
+ * scratch.  params NULL = the defaults.  Enqueued on `stream`; asynchronous
+ * unless ms is given, in which case it waits and *ms = the passes' device time
+ * (HIP events).  Allocates nothing and touches no render or query state
+ * (learned orders, graphs, async slots, accumulation sums, "plain_kernels").
+ * The outputs must not overlap the inputs, the workspace or each other.
+ * RT_ERR_INVALID_ARG: a null input, both outputs null, a bad size or
+ * parameter, a misaligned buffer, an overlap. */
+int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radiance, const rt_hit* d_hits,
+                      const rt_denoise_params* params, void* d_workspace,
+                      void* d_out_rgba, float* d_out_radiance, void* stream, double* ms);
+/* rt_render followed by the filter, synchronous, into HOST memory (out_rgba
+ * required, out_radiance nullable): the frame is rendered into a device
+ * radiance buffer exactly as rt_render_tile_device renders it (so it learns
+ * tile orders as that call does, and extension bit 4's accumulated frame is
+ * what gets filtered), its hit records come from rt_render_hits_device, then
+ * rt_denoise_device runs and the result is copied back.  stats (nullable): the
+ * render's counters, ms = the render's device time + the filter's.  The
+ * buffers belong to the context, grow on demand and are freed by rt_destroy.
+ * RT_ERR_INVALID_ARG on a context of several devices (whole frames only) and
+ * while spheres are active (extensions bit 8 with spheres uploaded: the hit
+ * buffer sees triangles only). */
+int rt_render_denoised(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                       const rt_denoise_params* params, uint8_t* out_rgba, float* out_radiance, rt_stats* stats);
+
 /* Schedule options (no effect on results, which are identical for every
  * setting):
  *   "kernel"        0 only: the one kernel, one lane per pixel (the
@@ -510,6 +562,16 @@ int rt_pick(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int x,
  *                   faster than 16x4, 6% than 32x2, profiles/r02/tiles)
  *   "wave_tile_used" (rt_get_option only) the tile shape s the current scene
  *                   gets on device 0
+ *   "denoise_kernel" rt_denoise_device's passes: 1 = the plain form (one lane
+ *                   per pixel, taps from global memory), 2 = the tiled form (a
+ *                   workgroup per 32x8 pixels of one residue class, the halo
+ *                   tile in LDS), 0 (default) = per step size the form
+ *                   measured faster.  Same results; 1 and 2
+ *                   are for tests and tools/denoise_bench.py
+ *   "denoise_pass"  rt_denoise_device: i in 0..5 = only pass i is enqueued, on
+ *                   whatever an earlier call left in the workspace
+ *                   (tools/denoise_bench.py times a pass this way; the output
+ *                   is meaningless); -1 (default) = every pass
  *   "extensions"    NON-REFERENCE features, bits (default 0 = the reference's
  *                   shader exactly):
  *                   1 = honour sky_enabled (@68): a miss is black when it is 0

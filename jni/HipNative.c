@@ -138,6 +138,32 @@ JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_pick(JNIEnv* env, 
     if (rc) throw_rt(env, rc);
 }
 
+/* void renderDenoised(long ctx, ByteBuffer ubo80, int w, int h, int maxBounces, int iterations, int normalPowerLog2,
+ *                     float sigmaDepth, float sigmaColor, ByteBuffer outRgba)
+ * One frame rendered and filtered by the edge-avoiding denoiser (rtamd.h rt_render_denoised; the parameters are
+ * rt_denoise_params, whose defaults are 4, 7, 0.005f, 0.5f) into a direct buffer of at least w * h * 4 bytes.
+ * Synchronous; on the thread that owns ctx. */
+JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_renderDenoised(JNIEnv* env, jclass c, jlong ctx,
+        jobject ubo, jint w, jint h, jint maxBounces, jint iterations, jint normalPowerLog2, jfloat sigmaDepth,
+        jfloat sigmaColor, jobject out) {
+    /* a heap (non-direct) buffer has capacity -1; the size check needs a sane frame size first */
+    if (!ubo || !out || w < 1 || h < 1 || (*env)->GetDirectBufferCapacity(env, ubo) < (jlong)sizeof(rt_camera_ubo) ||
+        (*env)->GetDirectBufferCapacity(env, out) < (jlong)w * (jlong)h * 4) {
+        jclass ex = (*env)->FindClass(env, "java/lang/RuntimeException");
+        if (ex) (*env)->ThrowNew(env, ex, "renderDenoised: need direct buffers of >= 80 bytes (camera UBO) and >= w * h * 4 "
+                                          "bytes (frame), w and h >= 1");
+        return;
+    }
+    rt_denoise_params p;
+    p.iterations = iterations;
+    p.normal_power_log2 = normalPowerLog2;
+    p.sigma_depth = sigmaDepth;
+    p.sigma_color = sigmaColor;
+    int rc = rt_render_denoised((rt_ctx*)(intptr_t)ctx, (const rt_camera_ubo*)(*env)->GetDirectBufferAddress(env, ubo),
+                                w, h, maxBounces, &p, (uint8_t*)(*env)->GetDirectBufferAddress(env, out), NULL, NULL);
+    if (rc) throw_rt(env, rc);
+}
+
 JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_destroy(JNIEnv* env, jclass c, jlong ctx) {
     rt_destroy((rt_ctx*)(intptr_t)ctx);
 }

@@ -32,6 +32,9 @@ public class HipEngine implements Runnable {
     private long submitted = 0;
     private Camera currentCamera = null;
     private int isSkyEnabled = 1;
+    private volatile boolean denoise = false;                             // setDenoise: filter every frame
+    private int dnIterations = 4, dnNormalPowerLog2 = 7;                  // rt_denoise_default_params
+    private float dnSigmaDepth = 0.005f, dnSigmaColor = 0.5f;
 
     public HipEngine(AtomicReference<FrameData> frameQueue) {
         this.frameQueue = frameQueue;
@@ -50,6 +53,15 @@ public class HipEngine implements Runnable {
      *  on the render thread, which owns the context (rt_pick; a context is single-thread-affine). */
     public void submitPick(int x, int y, java.util.function.IntConsumer onHit) {
         pickQueue.add(new Object[]{x, y, onHit});
+    }
+
+    /** Filter every frame with the edge-avoiding denoiser (rt_render_denoised, its default parameters): the
+     *  frames are then rendered synchronously, one at a time, instead of IN_FLIGHT at once. */
+    public void setDenoise(boolean on) { denoise = on; }
+    /** One denoised frame of the given UBO into a direct RGBA8 buffer; on the render thread. */
+    private void renderDenoised(ByteBuffer cameraUbo, ByteBuffer outRgba) {
+        HipNative.renderDenoised(ctx, cameraUbo, WIDTH, HEIGHT, MAX_BOUNCES, dnIterations, dnNormalPowerLog2,
+                                 dnSigmaDepth, dnSigmaColor, outRgba);
     }
 
     @Override public void run() {
@@ -86,6 +98,15 @@ public class HipEngine implements Runnable {
                 while ((pk = pickQueue.poll()) != null) {
                     HipNative.pick(ctx, ubo, WIDTH, HEIGHT, (Integer) pk[0], (Integer) pk[1], hit);
                     ((java.util.function.IntConsumer) pk[2]).accept(hit.getInt(4));   // rt_hit.tri
+                }
+                if (denoise) {                                            // synchronous: render, hits, filter, copy
+                    for (int j = 0; j < IN_FLIGHT; j++)                   // frames the pipelined loop left in flight
+                        if (tickets[j] != 0) { HipNative.waitFrame(ctx, tickets[j]); tickets[j] = 0; }   // (tickets are >= 1)
+                    submitted = 0;
+                    ByteBuffer px = ByteBuffer.allocateDirect(WIDTH * HEIGHT * 4);
+                    renderDenoised(ubo, px);
+                    frameQueue.set(new FrameData(px));
+                    continue;
                 }
                 // IN_FLIGHT (= the library's async_slots, default 4) frames in
                 // flight, each tracing on its own stream: the frames' traces

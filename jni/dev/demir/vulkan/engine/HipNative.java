@@ -21,4 +21,9 @@ final class HipNative {
     /** rt_pick: the hit record of pixel (x, y) into outHit (direct, >= 32 bytes, native order: float t, int tri,
      *  float normal[3], float pos[3]); tri < 0 = nothing hit.  On the thread that owns ctx. */
     static native void pick(long ctx, ByteBuffer ubo80, int w, int h, int x, int y, ByteBuffer outHit);
+    /** rt_render_denoised: one frame rendered and filtered by the edge-avoiding denoiser (rt_denoise_params:
+     *  defaults 4, 7, 0.005f, 0.5f) into outRgba (direct, >= w * h * 4 bytes).  Synchronous; on the thread that
+     *  owns ctx; one device, no active spheres. */
+    static native void renderDenoised(long ctx, ByteBuffer ubo80, int w, int h, int maxBounces, int iterations,
+                                      int normalPowerLog2, float sigmaDepth, float sigmaColor, ByteBuffer outRgba);
 }
