@@ -120,6 +120,7 @@ constexpr int kExtSkyToggle = 1;    // a miss is black when sky_enabled == 0
 constexpr int kExtEmissive = 2;     // a type-3 hit ends the path with attenuation * albedo
 constexpr int kExtAccumulate = 4;   // seed += frame_count*W*H; output sqrt(mean of linear colour)
 constexpr int kExtSpheres = 8;      // spheres (rt_upload_spheres) after the BVH walk, in index order
+constexpr int kExtNewSample = 16;   // seed += frame_count*W*H as kExtAccumulate moves it, and nothing else
 
 constexpr int kMaxBatch = 16;  // frames per launch (rt_render_batch_device)
 
@@ -152,7 +153,7 @@ struct TraceArgs {
                                 //   time through the scalar cache (solo_walk, rt_trace.hip; 0 = never)
     int      ext;               // non-reference extensions, kExt* bits (0 = the reference)
     int      sky_enabled;       // CameraUBO.sky_enabled (@68), read only with kExtSkyToggle
-    int      frame_count;       // CameraUBO.frame_count (@64), read only with kExtAccumulate
+    int      frame_count;       // CameraUBO.frame_count (@64), read only with kExtAccumulate / kExtNewSample
     float*   accum;             // kExtAccumulate: running linear-colour sums, 3 floats per pixel (tw*th)
     int      walk;              // 0 = one node per step (nodes/leafs), 2 = the same software-pipelined
                                 //   over the compact records (nodes2/leafs2; default)
@@ -280,5 +281,30 @@ struct DenoiseArgs {
     int           only_pass;    // option denoise_pass: -1 = every pass, i = pass i alone (timing)
 };
 hipError_t launch_denoise(const DenoiseArgs& d, hipStream_t stream);
+
+// rt_temporal.hip: the temporal accumulation's one kernel (rtamd.h
+// rt_temporal_device), enqueued on `stream`; validated
+// arguments, nothing allocated.
+struct TemporalBasis {          // rt_temporal_camera_basis's 13 floats
+    float ox, oy, oz;           // origin
+    float nx, ny, nz;           // N = cross(horizontal, vertical)
+    float ax, ay, az;           // A = cross(vertical, a), a = lower_left - origin
+    float bx, by, bz;           // B = cross(a, horizontal)
+    float det;                  // dot(a, N)
+};
+struct TemporalArgs {
+    int           width, height;
+    const float*  radiance;     // the render's radiance, 3 floats per pixel
+    const float4* hits;         // rt_hit records, 2 float4 per pixel
+    const float4* hist_prev;    // (c.rgb, n) per pixel, or null: no history
+    const float4* hits_prev;    // the previous frame's rt_hit records (null with hist_prev)
+    TemporalBasis cur, prev;
+    float         plane_tol, normal_min, max_history;   // max_history as a float (1..1024: exact)
+    float4*       hist_out;
+    uchar4*       out_rgba;     // nullable
+    float*        out_rad;      // nullable
+    int           form;         // option temporal_tile: 0 = the shipped form, 1 = 64 x 1 waves, 2 = 16 x 4
+};
+hipError_t launch_temporal(const TemporalArgs& t, hipStream_t stream);
 
 }  // namespace rtamd

@@ -316,6 +316,16 @@ struct PerDevice {
     // records, filter workspace and filtered outputs, grown on demand
     char*        d_denoise = nullptr;
     size_t       denoise_cap = 0;    // bytes
+    // rt_render_temporal: one allocation holding the frame's radiance, the two
+    // history / hit buffer pairs that ping-pong, the outputs and (with a
+    // spatial filter) its workspace, grown on demand; and the sequence's state:
+    // the pair the last frame wrote, its camera and size (temporal_valid: there
+    // is a history to reproject)
+    char*        d_temporal = nullptr;
+    size_t       temporal_cap = 0;   // bytes
+    bool         temporal_valid = false;
+    int          temporal_last = 0, temporal_w = 0, temporal_h = 0;
+    rt_camera_ubo temporal_cam = {};
 };
 
 static constexpr size_t kMaxOrders = 16;
@@ -381,6 +391,8 @@ struct rt_ctx {
                                    //   finish one ray at a time through the scalar cache (solo_walk, rt_trace.hip;
                                    //   0 = off); -1 (default) = 1 there, 0 elsewhere
     int  ext = 0;                  // non-reference extensions (kExt* bits), off by default
+    int  new_sample = 0;           // 1 = kExtNewSample for every launch: seed += frame_count*W*H and nothing else
+                                   //   (an option of its own: "extensions" keeps its four bits)
     int  walk = 2;                 // 0 = node per step, 2 = node per step, software-pipelined over the
                                    //   compact records (fastest measured)
     int  coop_walk = 0;            // cooperative walks: 0 = 64-node windows, 1 = preorder frontier
@@ -420,6 +432,8 @@ struct rt_ctx {
     int  denoise_kernel = 0;       // rt_denoise_device: 0 = per step size the form measured faster, 1 = the
                                    //   plain form, 2 = the tiled form (rt_denoise.hip; same results)
     int  denoise_pass = -1;        // rt_denoise_device: i >= 0 = enqueue pass i alone (tools/denoise_bench.py)
+    int  temporal_tile = 0;        // rt_temporal_device: 0 = the lane mapping measured faster, 1 = a wave on 64
+                                   //   pixels of a row, 2 = on a 16x4 tile (rt_temporal.hip; same results)
     int  split_bounce = 0;         // accel walk: paths alive at this bounce finish in a second kernel
                                    //   (0 = one kernel)
     // At the next upload: 0 = the reference's tree and order; 1 / 8 = the
@@ -878,7 +892,7 @@ static int set_schedule(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_
     a.coop_walk = p.scene.n_layouts ? 0 : ctx->coop_walk;
     a.coop_win = coop_window_of(ctx, p);
     a.block_waves = ctx->block_waves;
-    a.ext = ctx->ext;
+    a.ext = ctx->ext | (ctx->new_sample ? kExtNewSample : 0);
     a.solo_lanes = p.last_solo = solo_lanes_of(ctx, p.scene, a.coop_lanes, a.ext);
     a.scene.spheres = p.d_spheres;
     a.scene.n_spheres = (a.ext & kExtSpheres) ? p.n_spheres : 0;
@@ -886,6 +900,11 @@ static int set_schedule(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_
     a.sky_enabled = cam->sky_enabled;
     a.frame_count = cam->frame_count;
     a.accum = nullptr;
+    if ((a.ext & kExtNewSample) && !(a.ext & kExtAccumulate) && a.n_frames != 1) {
+        // (a launch carries one frame_count, its first camera's: the rule of the accumulation extension)
+        set_error("option new_sample renders one frame per launch (a launch carries one frame_count)");
+        return RT_ERR_INVALID_ARG;
+    }
     if (a.ext & kExtAccumulate) {
         if (a.n_frames != 1) {
             set_error("the accumulation extension renders one frame per launch (its sums are per pixel)");
@@ -1224,6 +1243,7 @@ int rt_destroy(rt_ctx* ctx) {
         if (p.d_spheres) (void)hipFree(p.d_spheres);
         if (p.d_query) (void)hipFree(p.d_query);
         if (p.d_denoise) (void)hipFree(p.d_denoise);
+        if (p.d_temporal) (void)hipFree(p.d_temporal);
         if (p.d_rgba) (void)hipFree(p.d_rgba);
         if (p.d_rad) (void)hipFree(p.d_rad);
         if (p.ev0) (void)hipEventDestroy(p.ev0);
@@ -1435,6 +1455,7 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
     ctx->max_depth = hs.max_depth;
     ctx->has_scene = true;
     ++ctx->scene_gen;
+    for (PerDevice& p : ctx->dev) p.temporal_valid = false;   // rt_render_temporal starts a new sequence
     free_host_scene(&hs);
     return RT_OK;
 }
@@ -1472,6 +1493,7 @@ int rt_upload_spheres(rt_ctx* ctx, const float* spheres, int n_spheres) {
         p.n_spheres = n_spheres;
     }
     ++ctx->scene_gen;    // learned tile orders see the new work
+    for (PerDevice& p : ctx->dev) p.temporal_valid = false;   // rt_render_temporal starts a new sequence
     return RT_OK;
 }
 
@@ -1875,6 +1897,202 @@ int rt_render_denoised(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int hei
     if (out_radiance)
         RT_HIP_CHECK(hipMemcpyAsync(out_radiance, p.d_denoise + o_rad, px * 12, hipMemcpyDeviceToHost, p.stream));
     RT_HIP_CHECK(hipStreamSynchronize(p.stream));
+    return RT_OK;
+}
+
+// ----------------------------------------------------------------- temporal --
+// Like the filter, rt_temporal_device reads and writes the caller's buffers
+// only, and its kernel is not counted in plain_kernels.
+static int check_temporal_params(const rt_temporal_params* q, const char* fn) {
+    if (q->max_history < 1 || q->max_history > 1024) {
+        set_error("%s: max_history must be in [1, 1024], got %d", fn, q->max_history);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite(q->plane_tol) || !(q->plane_tol > 0.0f) || !(q->normal_min >= -1.0f) ||
+        !(q->normal_min <= 1.0f)) {
+        set_error("%s: plane_tol must be finite and > 0 and normal_min in [-1, 1], got %g and %g", fn,
+                  (double)q->plane_tol, (double)q->normal_min);
+        return RT_ERR_INVALID_ARG;
+    }
+    return RT_OK;
+}
+
+static TemporalBasis temporal_basis_of(const rt_camera_ubo* cam) {
+    float b[13];
+    (void)rt_temporal_camera_basis(cam, b);
+    return TemporalBasis{b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], b[9], b[10], b[11], b[12]};
+}
+
+int rt_temporal_device(rt_ctx* ctx, int width, int height, const rt_camera_ubo* cam, const float* d_radiance,
+                       const rt_hit* d_hits, const rt_camera_ubo* prev_cam, const void* d_hist_prev,
+                       const rt_hit* d_hits_prev, const rt_temporal_params* params, void* d_hist_out,
+                       void* d_out_rgba, float* d_out_radiance, void* stream, double* ms) {
+    if (!ctx || !cam || !d_radiance || !d_hits || !d_hist_out) {
+        set_error("rt_temporal_device: null context, camera, input or d_hist_out");
+        return RT_ERR_INVALID_ARG;
+    }
+    const int n_prev = (prev_cam != nullptr) + (d_hist_prev != nullptr) + (d_hits_prev != nullptr);
+    if (n_prev != 0 && n_prev != 3) {
+        set_error("rt_temporal_device: prev_cam, d_hist_prev and d_hits_prev must be all null or all given");
+        return RT_ERR_INVALID_ARG;
+    }
+    if (rt_denoise_workspace_bytes(width, height) == 0) {
+        set_error("rt_temporal_device: bad frame size %dx%d", width, height);
+        return RT_ERR_INVALID_ARG;
+    }
+    rt_temporal_params q;
+    rt_temporal_default_params(&q);
+    if (params) q = *params;
+    if (int rc = check_temporal_params(&q, "rt_temporal_device")) return rc;
+    if ((((uintptr_t)d_hits | (uintptr_t)d_hits_prev | (uintptr_t)d_hist_prev | (uintptr_t)d_hist_out) & 15u) ||
+        (((uintptr_t)d_radiance | (uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
+        set_error("rt_temporal_device: the hit and history buffers must be 16-byte aligned, the other buffers 4-byte");
+        return RT_ERR_INVALID_ARG;
+    }
+    const size_t px = (size_t)width * (size_t)height;
+    struct Range { const void* p; size_t n; const char* name; };
+    const Range in[4] = {{d_radiance, px * 12, "d_radiance"}, {d_hits, px * 32, "d_hits"},
+                         {d_hist_prev, px * 16, "d_hist_prev"}, {d_hits_prev, px * 32, "d_hits_prev"}};
+    const Range out[3] = {{d_hist_out, px * 16, "d_hist_out"}, {d_out_rgba, px * 4, "d_out_rgba"},
+                          {d_out_radiance, px * 12, "d_out_radiance"}};
+    for (int o = 0; o < 3; ++o) {
+        if (!out[o].p) continue;
+        for (const Range& i : in)
+            if (i.p && ranges_overlap(out[o].p, out[o].n, i.p, i.n)) {
+                set_error("rt_temporal_device: %s overlaps %s", out[o].name, i.name);
+                return RT_ERR_INVALID_ARG;
+            }
+        for (int o2 = 0; o2 < o; ++o2)
+            if (out[o2].p && ranges_overlap(out[o].p, out[o].n, out[o2].p, out[o2].n)) {
+                set_error("rt_temporal_device: %s overlaps %s", out[o].name, out[o2].name);
+                return RT_ERR_INVALID_ARG;
+            }
+    }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TemporalArgs t;
+    t.width = width; t.height = height;
+    t.radiance = d_radiance;
+    t.hits = reinterpret_cast<const float4*>(d_hits);
+    t.hist_prev = static_cast<const float4*>(d_hist_prev);
+    t.hits_prev = reinterpret_cast<const float4*>(d_hits_prev);
+    t.cur = temporal_basis_of(cam);
+    t.prev = temporal_basis_of(prev_cam ? prev_cam : cam);
+    t.plane_tol = q.plane_tol;
+    t.normal_min = q.normal_min;
+    t.max_history = (float)q.max_history;
+    t.hist_out = static_cast<float4*>(d_hist_out);
+    t.out_rgba = static_cast<uchar4*>(d_out_rgba);
+    t.out_rad = d_out_radiance;
+    t.form = ctx->temporal_tile;
+    if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
+    RT_HIP_CHECK(launch_temporal(t, s));
+    if (ms) {
+        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
+        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
+        float e = 0.0f;
+        RT_HIP_CHECK(hipEventElapsedTime(&e, p.ev0, p.ev1));
+        *ms = (double)e;
+    }
+    return RT_OK;
+}
+
+int rt_render_temporal(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                       const rt_temporal_params* tparams, const rt_denoise_params* dparams, uint32_t flags,
+                       uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
+    int rc = check_render_args(ctx, cam, width, height, max_bounces, "rt_render_temporal");
+    if (rc) return rc;
+    if (!out_rgba) { set_error("rt_render_temporal: out_rgba is required"); return RT_ERR_INVALID_ARG; }
+    if (flags & ~(uint32_t)(RT_TEMPORAL_RESET | RT_TEMPORAL_FIXED_SEED)) {
+        set_error("rt_render_temporal: unknown flags 0x%x", flags);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (ctx->dev.size() != 1) {
+        set_error("rt_render_temporal: the context has %zu devices; the history belongs to whole frames of one device",
+                  ctx->dev.size());
+        return RT_ERR_INVALID_ARG;
+    }
+    PerDevice& p = ctx->dev[0];
+    if ((ctx->ext & kExtSpheres) && p.n_spheres > 0) {
+        set_error("rt_render_temporal: spheres are active (extensions bit 8); the hit buffer sees triangles only");
+        return RT_ERR_INVALID_ARG;
+    }
+    if (ctx->ext & kExtAccumulate) {
+        set_error("rt_render_temporal: extensions bit 4 (accumulation) is set; the frame would be averaged twice");
+        return RT_ERR_INVALID_ARG;
+    }
+    if (tparams)
+        if (int rq = check_temporal_params(tparams, "rt_render_temporal")) return rq;
+    if (dparams)
+        if (int rq = check_denoise_params(dparams, "rt_render_temporal")) return rq;
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    // per pixel: radiance (12 B), two histories (16 B each), two hit buffers (32 B each), the temporal
+    // radiance (12 B), RGBA8 (4 B); with a filter its workspace (32 B) and radiance (12 B) behind them.
+    // Each part on a 256-byte boundary.
+    const size_t px = (size_t)width * (size_t)height;
+    const auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t o_hist = up(px * 12), o_hits = o_hist + 2 * up(px * 16), o_trad = o_hits + 2 * up(px * 32),
+                 o_rgba = o_trad + up(px * 12), o_ws = o_rgba + up(px * 4), o_frad = o_ws + up(px * 32),
+                 total = dparams ? o_frad + up(px * 12) : o_ws;
+    if ((flags & RT_TEMPORAL_RESET) || width != p.temporal_w || height != p.temporal_h) p.temporal_valid = false;
+    if (total > p.temporal_cap) {
+        char* grown = nullptr;
+        const hipError_t e = hipMalloc(&grown, total);
+        if (e != hipSuccess) {
+            set_error("rt_render_temporal: %zu bytes of frame buffers: %s", total, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+        }
+        if (p.d_temporal) {
+            // (the call is synchronous: nothing in flight)  A sequence that gains a filter keeps its history.
+            if (p.temporal_valid)
+                RT_HIP_CHECK(hipMemcpy(grown, p.d_temporal, std::min(o_ws, p.temporal_cap), hipMemcpyDeviceToDevice));
+            (void)hipFree(p.d_temporal);
+        }
+        p.d_temporal = grown;
+        p.temporal_cap = total;
+    }
+    char* const base = p.d_temporal;
+    const bool hist = p.temporal_valid;          // the last call's history, hit buffer and camera
+    const int cur = hist ? 1 - p.temporal_last : 0, prev = 1 - cur;
+    float* d_rad = reinterpret_cast<float*>(base);
+    char* d_hist[2] = {base + o_hist, base + o_hist + up(px * 16)};
+    rt_hit* d_hits[2] = {reinterpret_cast<rt_hit*>(base + o_hits), reinterpret_cast<rt_hit*>(base + o_hits + up(px * 32))};
+    float* d_trad = reinterpret_cast<float*>(base + o_trad);
+    // the ordinary render of the frame, with a new sample per frame_count for this launch
+    const int new_sample = ctx->new_sample;
+    if (!(flags & RT_TEMPORAL_FIXED_SEED)) ctx->new_sample = 1;
+    rc = rt_render_tile_device(ctx, cam, width, height, max_bounces, 0, 0, width, height, nullptr, d_rad, p.stream,
+                               stats);
+    ctx->new_sample = new_sample;
+    if (rc) return rc;
+    rc = rt_render_hits_device(ctx, cam, width, height, 0, 0, width, height, 0, d_hits[cur], p.stream, nullptr);
+    if (rc) return rc;
+    const bool filter = dparams != nullptr;
+    double t_ms = 0.0, dn_ms = 0.0;
+    p.temporal_valid = false;                    // (a failure below leaves no half-written history behind)
+    rc = rt_temporal_device(ctx, width, height, cam, d_rad, d_hits[cur], hist ? &p.temporal_cam : nullptr,
+                            hist ? d_hist[prev] : nullptr, hist ? d_hits[prev] : nullptr, tparams, d_hist[cur],
+                            filter ? nullptr : base + o_rgba, (filter || out_radiance) ? d_trad : nullptr, p.stream,
+                            stats ? &t_ms : nullptr);
+    if (rc) return rc;
+    const float* d_final_rad = d_trad;
+    if (filter) {
+        float* d_frad = reinterpret_cast<float*>(base + o_frad);
+        rc = rt_denoise_device(ctx, width, height, d_trad, d_hits[cur], dparams, base + o_ws, base + o_rgba,
+                               out_radiance ? d_frad : nullptr, p.stream, stats ? &dn_ms : nullptr);
+        if (rc) return rc;
+        d_final_rad = d_frad;
+    }
+    if (stats) stats->ms += t_ms + dn_ms;
+    RT_HIP_CHECK(hipMemcpyAsync(out_rgba, base + o_rgba, px * 4, hipMemcpyDeviceToHost, p.stream));
+    if (out_radiance)
+        RT_HIP_CHECK(hipMemcpyAsync(out_radiance, d_final_rad, px * 12, hipMemcpyDeviceToHost, p.stream));
+    RT_HIP_CHECK(hipStreamSynchronize(p.stream));
+    p.temporal_valid = true;
+    p.temporal_last = cur;
+    p.temporal_w = width; p.temporal_h = height;
+    p.temporal_cam = *cam;
     return RT_OK;
 }
 
@@ -2446,6 +2664,7 @@ static const Option kOptions[] = {
     in_range("coop_lanes", &rt_ctx::coop_lanes, -1, 64),
     in_range("solo_lanes", &rt_ctx::solo_lanes, -1, 64),
     in_range("extensions", &rt_ctx::ext, 0, 15),
+    one_of("new_sample", &rt_ctx::new_sample, 0, 1),
     one_of("walk", &rt_ctx::walk, 0, 2),
     one_of("coop_window", &rt_ctx::coop_window, 0, 32, 64),
     one_of("coop_walk", &rt_ctx::coop_walk, 0, 1),
@@ -2478,6 +2697,7 @@ static const Option kOptions[] = {
     in_range("wave_tile", &rt_ctx::wave_tile, -1, 3),
     in_range("denoise_kernel", &rt_ctx::denoise_kernel, 0, 2),
     in_range("denoise_pass", &rt_ctx::denoise_pass, -1, 5),
+    in_range("temporal_tile", &rt_ctx::temporal_tile, 0, 2),
 };
 
 static const Option* find_option(const char* name) {

@@ -1,0 +1,172 @@
+// rt_temporal.hip — temporal accumulation reprojected through the first-hit
+// buffer (rtamd.h "temporal").
+//
+// One kernel.  A pixel with a hit projects its world position through the
+// current and the previous camera, follows the difference to where the surface
+// was in the previous frame, gathers the up to four history records around
+// that point whose own first hits lie on the same plane with the same normal,
+// and blends the new sample into their bilinear mean with weight 1 / n.  A
+// pixel without a hit, or one whose history is rejected, starts again from its
+// own sample.  All arithmetic is IEEE binary32 in the order DESIGN.md §4h
+// writes it (the library is built with -ffp-contract=off, `/` and sqrtf are
+// correctly rounded, fminf drops a NaN operand), so tests/temporal_ref.py
+// restates it bit for bit.
+//
+// A memory-bound gather: a pixel reads its own 12 + 32 B, each tap 48 B (the
+// two 16-B halves of the previous hit record and one 16-B history record), and
+// writes 16 + 12 + 4 B.  The four taps' twelve loads are issued together from
+// clamped addresses and their contributions predicated, so no load waits for a
+// branch.  Two lane mappings of the same 64 x 4-pixel workgroup:
+//   rows  : a wave on 64 consecutive pixels of one row
+//   tiles : a wave on a 16 x 4 tile (the render's wave tile on the accel tree)
+// Which one ships was measured (kShippedForm below).
+#include "rt_internal.h"
+
+#include <cmath>
+
+namespace rtamd {
+namespace {
+
+__device__ __forceinline__ uint8_t unorm8(float c) {   // the render's store (rt_trace.hip)
+    return c > 0.0f ? (c < 1.0f ? (uint8_t)__builtin_rintf(c * 255.0f) : (uint8_t)255) : (uint8_t)0;
+}
+
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+    return (ax * bx + ay * by) + az * bz;
+}
+
+// project(C, P) of DESIGN.md §4h: the viewport coordinates whose ray from C's origin passes through P
+__device__ __forceinline__ bool project(const TemporalBasis& c, float px, float py, float pz, float& u, float& v) {
+    const float wx = px - c.ox, wy = py - c.oy, wz = pz - c.oz;
+    const float dn = dot3(wx, wy, wz, c.nx, c.ny, c.nz);
+    u = dot3(wx, wy, wz, c.ax, c.ay, c.az) / dn;
+    v = dot3(wx, wy, wz, c.bx, c.by, c.bz) / dn;
+    return dn * c.det > 0.0f;
+}
+
+template <bool TILES>
+__global__ __launch_bounds__(256) void temporal_kernel(TemporalArgs a, int tiles_x) {
+    const int bx = (int)(blockIdx.x % (unsigned)tiles_x), by = (int)(blockIdx.x / (unsigned)tiles_x);
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int x = bx * 64 + (TILES ? (int)(wave * 16u + (lane & 15u)) : (int)lane);
+    const int y = by * 4 + (TILES ? (int)(lane >> 4) : (int)wave);
+    if (x >= a.width || y >= a.height) return;
+    const int W = a.width, H = a.height;
+    const size_t p = (size_t)y * (size_t)W + (size_t)x;
+    const float4 p0 = a.hits[2 * p], p1 = a.hits[2 * p + 1];      // (t, tri, n.xy), (n.z, pos.xyz)
+    const float gr = a.radiance[3 * p + 0], gg = a.radiance[3 * p + 1], gb = a.radiance[3 * p + 2];
+    const float cr = gr * gr, cg = gg * gg, cb = gb * gb;
+    const bool hit = __float_as_int(p0.y) >= 0;
+    float orr = cr, og = cg, ob = cb, on = hit ? 1.0f : 0.0f;      // sky / invalid: passes through with n = 0
+    if (hit && a.hist_prev) {
+        const float nx = p0.z, ny = p0.w, nz = p1.x, qx = p1.y, qy = p1.z, qz = p1.w;
+        float uc, vc, up, vp;
+        const bool fc = project(a.cur, qx, qy, qz, uc, vc);
+        const bool fp = project(a.prev, qx, qy, qz, up, vp);
+        const float fW = (float)W, fH = (float)H;
+        const float fx = (float)x + (up - uc) * fW, fy = (float)y + (vc - vp) * fH;
+        if (fc && fp && fx > -1.0f && fx < fW && fy > -1.0f && fy < fH) {      // (a NaN fails)
+            const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
+            const float ax = fx - x0, ay = fy - y0, tol = a.plane_tol * p0.x;
+            const int ix = (int)x0, iy = (int)y0;
+            // the four taps' loads first, from addresses inside the frame either way
+            float4 h0[4], h1[4], hc[4];
+            bool inside[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int tx = ix + (k & 1), ty = iy + (k >> 1);
+                inside[k] = tx >= 0 && tx < W && ty >= 0 && ty < H;
+                const size_t q = inside[k] ? (size_t)ty * (size_t)W + (size_t)tx : p;
+                h0[k] = a.hits_prev[2 * q];
+                h1[k] = a.hits_prev[2 * q + 1];
+                hc[k] = a.hist_prev[q];
+            }
+            float sr = 0.0f, sg = 0.0f, sb = 0.0f, ws = 0.0f, nm = __builtin_inff();
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {                       // j outer, i inner
+                const float wt = ((k & 1) ? ax : 1.0f - ax) * ((k >> 1) ? ay : 1.0f - ay);
+                const float nd = dot3(nx, ny, nz, h0[k].z, h0[k].w, h1[k].x);
+                const float pd = __builtin_fabsf(dot3(nx, ny, nz, h1[k].y - qx, h1[k].z - qy, h1[k].w - qz));
+                const bool take = inside[k] && __float_as_int(h0[k].y) >= 0 && hc[k].w > 0.0f && wt > 0.0f &&
+                                  nd >= a.normal_min && pd <= tol;
+                sr = take ? sr + wt * hc[k].x : sr;
+                sg = take ? sg + wt * hc[k].y : sg;
+                sb = take ? sb + wt * hc[k].z : sb;
+                ws = take ? ws + wt : ws;
+                nm = take ? __builtin_fminf(nm, hc[k].w) : nm;
+            }
+            if (ws > 0.0f) {
+                const float hr = sr / ws, hg = sg / ws, hb = sb / ws;
+                const float nn = __builtin_fminf(nm + 1.0f, a.max_history), inv = 1.0f / nn;
+                orr = hr + (cr - hr) * inv;
+                og = hg + (cg - hg) * inv;
+                ob = hb + (cb - hb) * inv;
+                on = nn;
+            }
+        }
+    }
+    a.hist_out[p] = make_float4(orr, og, ob, on);
+    if (a.out_rgba || a.out_rad) {
+        const float rr = sqrtf(orr), rg = sqrtf(og), rb = sqrtf(ob);
+        if (a.out_rgba) a.out_rgba[p] = make_uchar4(unorm8(rr), unorm8(rg), unorm8(rb), 255);
+        if (a.out_rad) {
+            a.out_rad[3 * p + 0] = rr;
+            a.out_rad[3 * p + 1] = rg;
+            a.out_rad[3 * p + 2] = rb;
+        }
+    }
+}
+
+// The lane mapping option temporal_tile 0 takes: the faster one of
+// tools/temporal_bench.py's times on config 3 at 1920x1080 (profiles/temporal,
+// DESIGN.md §4h): rows 0.0364 ms [0.0364, 0.0365] against tiles 0.0371
+// [0.0370, 0.0372], with the camera orbiting 1 degree per frame.
+constexpr int kShippedForm = 1;
+
+}  // namespace
+
+hipError_t launch_temporal(const TemporalArgs& t, hipStream_t stream) {
+    const size_t tx = ((size_t)t.width + 63) / 64, ty = ((size_t)t.height + 3) / 4;   // <= 2^29 workgroups
+    const int form = t.form ? t.form : kShippedForm;
+    if (form == 2)
+        hipLaunchKernelGGL(temporal_kernel<true>, dim3((unsigned)(tx * ty)), dim3(256), 0, stream, t, (int)tx);
+    else
+        hipLaunchKernelGGL(temporal_kernel<false>, dim3((unsigned)(tx * ty)), dim3(256), 0, stream, t, (int)tx);
+    return hipGetLastError();
+}
+
+}  // namespace rtamd
+
+extern "C" {
+
+void rt_temporal_default_params(rt_temporal_params* out) {
+    if (!out) return;
+    out->max_history = 32;
+    out->plane_tol = 0.005f;
+    out->normal_min = 0.9f;
+    out->reserved = 0;
+}
+
+int rt_temporal_camera_basis(const rt_camera_ubo* cam, float out[13]) {
+    if (!cam || !out) {
+        rtamd::set_error("rt_temporal_camera_basis: null camera or output");
+        return RT_ERR_INVALID_ARG;
+    }
+    const float* o = cam->origin;
+    const float* h = cam->horizontal;
+    const float* v = cam->vertical;
+    const float a[3] = {cam->lower_left[0] - o[0], cam->lower_left[1] - o[1], cam->lower_left[2] - o[2]};
+    const auto cross = [](const float* p, const float* q, float* r) {
+        r[0] = p[1] * q[2] - p[2] * q[1];
+        r[1] = p[2] * q[0] - p[0] * q[2];
+        r[2] = p[0] * q[1] - p[1] * q[0];
+    };
+    out[0] = o[0]; out[1] = o[1]; out[2] = o[2];
+    cross(h, v, out + 3);       // N
+    cross(v, a, out + 6);       // A
+    cross(a, h, out + 9);       // B
+    out[12] = (a[0] * out[3] + a[1] * out[4]) + a[2] * out[5];
+    return RT_OK;
+}
+
+}  // extern "C"

@@ -1238,7 +1238,7 @@ void trace_simple(TraceArgs a) {
         }
     } else if (pixel) {
         const int x = a.x0 + lx, y = frame_row(a, fr_i, ly);
-        if ((FEAT & kFeatExt) && (a.ext & kExtAccumulate)) {
+        if ((FEAT & kFeatExt) && (a.ext & (kExtAccumulate | kExtNewSample))) {
             // extension: a new sample per frame; frame 0 is the reference's seed (:164)
             seed = (uint32_t)(y * a.width + x) + (uint32_t)a.frame_count * (uint32_t)(a.width * a.height);
             primary_ray_seeded(a, fr_i, x, y, seed, o, d);

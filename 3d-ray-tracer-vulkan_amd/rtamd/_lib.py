@@ -40,12 +40,13 @@ EXPORTED = (
     "rt_build_id", "rt_render_batch_rect_device", "rt_render_batch_runs_device",
     "rt_query_rays_device", "rt_query_rays", "rt_render_hits_device", "rt_pick", "rt_build_scene_map",
     "rt_denoise_default_params", "rt_denoise_workspace_bytes", "rt_denoise_device", "rt_render_denoised",
+    "rt_temporal_default_params", "rt_temporal_camera_basis", "rt_temporal_device", "rt_render_temporal",
 )
 
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
 # "src=" field is the first 16 hex digits of SHA-256 over them concatenated.
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
-                 "csrc/rt_denoise.hip", "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h",
+                 "csrc/rt_denoise.hip", "csrc/rt_temporal.hip", "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h",
                  "csrc/accel_build.h", "../include/rtamd.h")
 
 
@@ -127,10 +128,21 @@ class DenoiseParams(C.Structure):       # rt_denoise_params; the defaults are rt
         super().__init__(iterations, normal_power_log2, sigma_depth, sigma_color)
 
 
+class TemporalParams(C.Structure):      # rt_temporal_params; the defaults are rt_temporal_default_params's
+    _fields_ = [("max_history", C.c_int32), ("plane_tol", C.c_float), ("normal_min", C.c_float),
+                ("reserved", C.c_int32)]
+
+    def __init__(self, max_history: int = 32, plane_tol: float = 0.005, normal_min: float = 0.9):
+        super().__init__(max_history, plane_tol, normal_min, 0)
+
+
 RT_QUERY_ANY = 1
+RT_TEMPORAL_RESET = 1           # rt_render_temporal's flags
+RT_TEMPORAL_FIXED_SEED = 2
 
 assert C.sizeof(CameraUBO) == 80
 assert C.sizeof(Ray) == 32 and C.sizeof(Hit) == 32 and C.sizeof(DenoiseParams) == 16
+assert C.sizeof(TemporalParams) == 16
 
 _lock = threading.Lock()
 _lib = None
@@ -211,6 +223,12 @@ def lib() -> C.CDLL:
                 "rt_denoise_device": (i32, [vp, i32, i32, vp, vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, dp]),
                 "rt_render_denoised": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, C.POINTER(DenoiseParams), vp, vp,
                                              C.POINTER(Stats)]),
+                "rt_temporal_default_params": (None, [C.POINTER(TemporalParams)]),
+                "rt_temporal_camera_basis": (i32, [C.POINTER(CameraUBO), fp]),
+                "rt_temporal_device": (i32, [vp, i32, i32, C.POINTER(CameraUBO), vp, vp, C.POINTER(CameraUBO), vp, vp,
+                                             C.POINTER(TemporalParams), vp, vp, vp, vp, dp]),
+                "rt_render_temporal": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, C.POINTER(TemporalParams),
+                                             C.POINTER(DenoiseParams), C.c_uint32, vp, vp, C.POINTER(Stats)]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)

@@ -20,7 +20,8 @@ from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._lib import RT_QUERY_ANY, CameraUBO, DenoiseParams, Hit, RtError, Stats, check, lib
+from ._lib import (RT_QUERY_ANY, RT_TEMPORAL_FIXED_SEED, RT_TEMPORAL_RESET, CameraUBO, DenoiseParams, Hit, RtError, Stats,
+                   TemporalParams, check, lib)
 from .scene import BuiltCpuData, Camera
 
 REFERENCE_WIDTH = 1280          # VulkanEngine.java:45
@@ -267,6 +268,71 @@ class Renderer:
                                        C.byref(st) if st is not None else None))
         return rgba, rad, (st.as_dict() if st is not None else None)
 
+    # --- temporal accumulation (include/rtamd.h "temporal") ---
+    def temporal_device(self, width: int, height: int, camera, d_radiance: int, d_hits: int, d_hist_out: int,
+                        prev_camera=None, d_hist_prev: Optional[int] = None, d_hits_prev: Optional[int] = None,
+                        d_out_rgba: Optional[int] = None, d_out_radiance: Optional[int] = None,
+                        params: Optional[TemporalParams] = None, stream: Optional[int] = None, ms: bool = False):
+        """Enqueue one frame of the accumulation between device buffers (raw
+        device pointers; rt_temporal_device) on a HIP stream handle: the new
+        frame's radiance, hit records and camera, the previous frame's camera,
+        history and hit records (all None: a first frame), the new history and
+        the optional display outputs.  Asynchronous unless ms, which waits and
+        returns the kernel's device time in milliseconds."""
+        t = C.c_double() if ms else None
+        check(lib().rt_temporal_device(self._ctx, width, height, C.byref(_ubo(camera)) if camera is not None else None,
+                                       d_radiance, d_hits,
+                                       C.byref(_ubo(prev_camera)) if prev_camera is not None else None, d_hist_prev,
+                                       d_hits_prev, C.byref(params) if params is not None else None, d_hist_out,
+                                       d_out_rgba, d_out_radiance, stream, C.byref(t) if t is not None else None))
+        return t.value if t is not None else None
+
+    def temporal(self, radiance, hits, camera, prev_camera=None, hist_prev=None, hits_prev=None,
+                 params: Optional[TemporalParams] = None):
+        """The accumulation on host arrays: radiance float32 [H, W, 3] and
+        HIT_DTYPE records [H, W] of the new frame and its camera; the previous
+        frame's camera, history float32 [H, W, 4] and hit records, or None for
+        a first frame.  Returns (history float32 [H, W, 4], rgba uint8
+        [H, W, 4], radiance float32 [H, W, 3])."""
+        import torch
+        rad = np.ascontiguousarray(radiance, dtype=np.float32)
+        h, w = rad.shape[:2]
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.float32).reshape(h, w, -1)).cuda()  # noqa: E731
+        with torch.cuda.device(self.device_ids[0]):
+            d_rad = torch.from_numpy(rad).cuda()
+            d_hit = dev(np.ascontiguousarray(hits, dtype=HIT_DTYPE))
+            d_hp = dev(np.ascontiguousarray(hist_prev, dtype=np.float32)) if hist_prev is not None else None
+            d_hq = dev(np.ascontiguousarray(hits_prev, dtype=HIT_DTYPE)) if hits_prev is not None else None
+            o_hist = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
+            o_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda")
+            o_rad = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+            self.temporal_device(w, h, camera, d_rad.data_ptr(), d_hit.data_ptr(), o_hist.data_ptr(), prev_camera,
+                                 d_hp.data_ptr() if d_hp is not None else None,
+                                 d_hq.data_ptr() if d_hq is not None else None, o_rgba.data_ptr(), o_rad.data_ptr(),
+                                 params, torch.cuda.current_stream().cuda_stream)
+            return o_hist.cpu().numpy(), o_rgba.cpu().numpy(), o_rad.cpu().numpy()
+
+    def render_temporal(self, camera, width: int, height: int, max_bounces: int = REFERENCE_MAX_BOUNCES,
+                        params: Optional[TemporalParams] = None, denoise: Optional[DenoiseParams] = None,
+                        reset: bool = False, fixed_seed: bool = False, radiance: bool = False, stats: bool = False):
+        """One frame of a temporally accumulated sequence (rt_render_temporal):
+        render with a new sample per camera.frame_count (fixed_seed: the
+        context's extensions as they are), first-hit buffer, reprojection of
+        the context's history of the previous call, and with `denoise` the
+        spatial filter after it.  reset drops the history first.  Returns
+        (rgba, radiance or None, stats dict or None); ms = render + temporal
+        (+ filter).  One device, no active spheres, extensions bit 4 off."""
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        rad = np.empty((height, width, 3), dtype=np.float32) if radiance else None
+        st = Stats() if stats else None
+        flags = (RT_TEMPORAL_RESET if reset else 0) | (RT_TEMPORAL_FIXED_SEED if fixed_seed else 0)
+        check(lib().rt_render_temporal(self._ctx, C.byref(_ubo(camera)), width, height, max_bounces,
+                                       C.byref(params) if params is not None else None,
+                                       C.byref(denoise) if denoise is not None else None, flags, rgba.ctypes.data,
+                                       rad.ctypes.data if rad is not None else None,
+                                       C.byref(st) if st is not None else None))
+        return rgba, rad, (st.as_dict() if st is not None else None)
+
 
 class PinnedFrame:
     """An RGBA8 frame in pinned host memory (rt_host_alloc), as a numpy view."""
@@ -324,15 +390,21 @@ class HipEngine:
     def __init__(self, frame_queue: AtomicReference, width: int = REFERENCE_WIDTH,
                  height: int = REFERENCE_HEIGHT, max_bounces: int = REFERENCE_MAX_BOUNCES,
                  device_ids: Sequence[int] = (0,), collect_stats: bool = False, pipelined: bool = True,
-                 inflight: int = 4, denoise: Optional[DenoiseParams] = None):
+                 inflight: int = 4, denoise: Optional[DenoiseParams] = None,
+                 temporal: Optional[TemporalParams] = None):
         self.frame_queue = frame_queue
         # pipelined: `inflight` frames in flight (rt_render_async, one slot and
         # trace stream each), so the frames' traces overlap each other and
         # their readbacks; the reference waits for each frame
         # (VulkanEngine.java:410-429).  Stats need the synchronous path.
         # denoise: every frame goes through render_denoised, which is synchronous.
+        # temporal: every frame goes through render_temporal (synchronous as well), frame k of the
+        # engine with frame_count k, so that every frame is a new sample; with denoise too, the
+        # filter runs after the accumulation.
         self.denoise = denoise
-        self.pipelined = pipelined and not collect_stats and denoise is None
+        self.temporal = temporal
+        self.temporal_frames = 0
+        self.pipelined = pipelined and not collect_stats and denoise is None and temporal is None
         self.inflight = max(1, min(8, int(inflight)))
         self.width, self.height, self.max_bounces = width, height, max_bounces
         self.device_ids = tuple(device_ids)
@@ -398,7 +470,12 @@ class HipEngine:
                 ubo = CameraUBO.from_buffer_copy(bytes(camera.ubo))
                 ubo.sky_enabled = self.is_sky_enabled        # written, ignored by the shader
                 if not self.pipelined:
-                    if self.denoise is not None:
+                    if self.temporal is not None:
+                        ubo.frame_count = self.temporal_frames
+                        rgba, _, st = renderer.render_temporal(ubo, self.width, self.height, self.max_bounces,
+                                                               self.temporal, self.denoise, stats=self.collect_stats)
+                        self.temporal_frames += 1
+                    elif self.denoise is not None:
                         rgba, _, st = renderer.render_denoised(ubo, self.width, self.height, self.max_bounces,
                                                                self.denoise, stats=self.collect_stats)
                     else:

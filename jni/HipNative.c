@@ -164,6 +164,38 @@ JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_renderDenoised(JNI
     if (rc) throw_rt(env, rc);
 }
 
+/* void renderTemporal(long ctx, ByteBuffer ubo80, int w, int h, int maxBounces, int maxHistory, float planeTol,
+ *                     float normalMin, int filterIterations, int flags, ByteBuffer outRgba)
+ * One frame of a temporally accumulated sequence (rtamd.h rt_render_temporal; the parameters are
+ * rt_temporal_params, whose defaults are 32, 0.005f, 0.9f) into a direct buffer of at least w * h * 4 bytes.  The
+ * host advances the UBO's frame_count per frame.  filterIterations 0 = no spatial filter, 1..6 = the denoiser's
+ * default parameters with that many passes after the accumulation; flags = RT_TEMPORAL_RESET (1) |
+ * RT_TEMPORAL_FIXED_SEED (2).  Synchronous; on the thread that owns ctx. */
+JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_renderTemporal(JNIEnv* env, jclass c, jlong ctx,
+        jobject ubo, jint w, jint h, jint maxBounces, jint maxHistory, jfloat planeTol, jfloat normalMin,
+        jint filterIterations, jint flags, jobject out) {
+    /* a heap (non-direct) buffer has capacity -1; the size check needs a sane frame size first */
+    if (!ubo || !out || w < 1 || h < 1 || (*env)->GetDirectBufferCapacity(env, ubo) < (jlong)sizeof(rt_camera_ubo) ||
+        (*env)->GetDirectBufferCapacity(env, out) < (jlong)w * (jlong)h * 4) {
+        jclass ex = (*env)->FindClass(env, "java/lang/RuntimeException");
+        if (ex) (*env)->ThrowNew(env, ex, "renderTemporal: need direct buffers of >= 80 bytes (camera UBO) and >= w * h * 4 "
+                                          "bytes (frame), w and h >= 1");
+        return;
+    }
+    rt_temporal_params t;
+    t.max_history = maxHistory;
+    t.plane_tol = planeTol;
+    t.normal_min = normalMin;
+    t.reserved = 0;
+    rt_denoise_params d;
+    rt_denoise_default_params(&d);
+    d.iterations = filterIterations;
+    int rc = rt_render_temporal((rt_ctx*)(intptr_t)ctx, (const rt_camera_ubo*)(*env)->GetDirectBufferAddress(env, ubo),
+                                w, h, maxBounces, &t, filterIterations != 0 ? &d : NULL, (uint32_t)flags,
+                                (uint8_t*)(*env)->GetDirectBufferAddress(env, out), NULL, NULL);
+    if (rc) throw_rt(env, rc);
+}
+
 JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_destroy(JNIEnv* env, jclass c, jlong ctx) {
     rt_destroy((rt_ctx*)(intptr_t)ctx);
 }

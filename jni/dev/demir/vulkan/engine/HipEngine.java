@@ -35,6 +35,10 @@ public class HipEngine implements Runnable {
     private volatile boolean denoise = false;                             // setDenoise: filter every frame
     private int dnIterations = 4, dnNormalPowerLog2 = 7;                  // rt_denoise_default_params
     private float dnSigmaDepth = 0.005f, dnSigmaColor = 0.5f;
+    private volatile boolean temporal = false;                            // setTemporal: accumulate across frames
+    private int tpMaxHistory = 32;                                        // rt_temporal_default_params
+    private float tpPlaneTol = 0.005f, tpNormalMin = 0.9f;
+    private int temporalFrames = 0;                                       // the frame_count of the next temporal frame
 
     public HipEngine(AtomicReference<FrameData> frameQueue) {
         this.frameQueue = frameQueue;
@@ -62,6 +66,17 @@ public class HipEngine implements Runnable {
     private void renderDenoised(ByteBuffer cameraUbo, ByteBuffer outRgba) {
         HipNative.renderDenoised(ctx, cameraUbo, WIDTH, HEIGHT, MAX_BOUNCES, dnIterations, dnNormalPowerLog2,
                                  dnSigmaDepth, dnSigmaColor, outRgba);
+    }
+
+    /** Accumulate samples across frames, following the camera (rt_render_temporal, its default parameters; with
+     *  setDenoise too, a 2-pass spatial filter after the accumulation): synchronous frames, like setDenoise. */
+    public void setTemporal(boolean on) { temporal = on; }
+    /** One temporal frame of the given UBO into a direct RGBA8 buffer; on the render thread.  Every frame gets a
+     *  frame_count of its own, so that it is a new sample. */
+    private void renderTemporal(ByteBuffer cameraUbo, ByteBuffer outRgba) {
+        cameraUbo.putInt(64, temporalFrames++);
+        HipNative.renderTemporal(ctx, cameraUbo, WIDTH, HEIGHT, MAX_BOUNCES, tpMaxHistory, tpPlaneTol, tpNormalMin,
+                                 denoise ? 2 : 0, 0, outRgba);
     }
 
     @Override public void run() {
@@ -99,12 +114,12 @@ public class HipEngine implements Runnable {
                     HipNative.pick(ctx, ubo, WIDTH, HEIGHT, (Integer) pk[0], (Integer) pk[1], hit);
                     ((java.util.function.IntConsumer) pk[2]).accept(hit.getInt(4));   // rt_hit.tri
                 }
-                if (denoise) {                                            // synchronous: render, hits, filter, copy
+                if (denoise || temporal) {                                // synchronous: render, hits, filter, copy
                     for (int j = 0; j < IN_FLIGHT; j++)                   // frames the pipelined loop left in flight
                         if (tickets[j] != 0) { HipNative.waitFrame(ctx, tickets[j]); tickets[j] = 0; }   // (tickets are >= 1)
                     submitted = 0;
                     ByteBuffer px = ByteBuffer.allocateDirect(WIDTH * HEIGHT * 4);
-                    renderDenoised(ubo, px);
+                    if (temporal) renderTemporal(ubo, px); else renderDenoised(ubo, px);
                     frameQueue.set(new FrameData(px));
                     continue;
                 }

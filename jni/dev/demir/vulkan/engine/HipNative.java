@@ -26,4 +26,12 @@ final class HipNative {
      *  owns ctx; one device, no active spheres. */
     static native void renderDenoised(long ctx, ByteBuffer ubo80, int w, int h, int maxBounces, int iterations,
                                       int normalPowerLog2, float sigmaDepth, float sigmaColor, ByteBuffer outRgba);
+    /** rt_render_temporal: one frame of a temporally accumulated sequence (rt_temporal_params: defaults 32, 0.005f,
+     *  0.9f) into outRgba (direct, >= w * h * 4 bytes); the caller advances the UBO's frame_count per frame.
+     *  filterIterations 0 = no spatial filter, 1..6 = the denoiser's defaults with that many passes; flags: 1 = drop
+     *  the history first, 2 = keep the context's extensions (no new sample per frame).  Synchronous; on the thread
+     *  that owns ctx; one device, no active spheres, extensions bit 4 off. */
+    static native void renderTemporal(long ctx, ByteBuffer ubo80, int w, int h, int maxBounces, int maxHistory,
+                                      float planeTol, float normalMin, int filterIterations, int flags,
+                                      ByteBuffer outRgba);
 }
