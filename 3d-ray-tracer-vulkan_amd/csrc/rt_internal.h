@@ -281,6 +281,10 @@ struct DenoiseArgs {
     int           only_pass;    // option denoise_pass: -1 = every pass, i = pass i alone (timing)
 };
 hipError_t launch_denoise(const DenoiseArgs& d, hipStream_t stream);
+// rt_denoise_history.hip: the history-adaptive filter's passes (rtamd.h
+// rt_denoise_history_device) on `hist`, width x height records
+// (c.rgb, n); d.radiance is not read.
+hipError_t launch_denoise_history(const DenoiseArgs& d, const float4* hist, hipStream_t stream);
 
 // rt_temporal.hip: the temporal accumulation's one kernel (rtamd.h
 // rt_temporal_device), enqueued on `stream`; validated

@@ -1772,45 +1772,49 @@ static int check_denoise_params(const rt_denoise_params* q, const char* fn) {
     return RT_OK;
 }
 
-int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radiance, const rt_hit* d_hits,
-                      const rt_denoise_params* params, void* d_workspace, void* d_out_rgba, float* d_out_radiance,
-                      void* stream, double* ms) {
-    if (!ctx || !d_radiance || !d_hits || !d_workspace) {
-        set_error("rt_denoise_device: null context or buffer");
+// rt_denoise_device (d_in = the render's radiance, 12 B per pixel) and rt_denoise_history_device (d_in = a
+// history buffer, 16 B per pixel, 16-byte aligned): the same checks, workspace and passes' timing.
+static int denoise_device(const char* fn, bool history, rt_ctx* ctx, int width, int height, const void* d_in,
+                          const rt_hit* d_hits, const rt_denoise_params* params, void* d_workspace, void* d_out_rgba,
+                          float* d_out_radiance, void* stream, double* ms) {
+    if (!ctx || !d_in || !d_hits || !d_workspace) {
+        set_error("%s: null context or buffer", fn);
         return RT_ERR_INVALID_ARG;
     }
-    if (!d_out_rgba && !d_out_radiance) { set_error("rt_denoise_device: both outputs are null"); return RT_ERR_INVALID_ARG; }
+    if (!d_out_rgba && !d_out_radiance) { set_error("%s: both outputs are null", fn); return RT_ERR_INVALID_ARG; }
     const size_t ws_bytes = rt_denoise_workspace_bytes(width, height);
-    if (ws_bytes == 0) { set_error("rt_denoise_device: bad frame size %dx%d", width, height); return RT_ERR_INVALID_ARG; }
+    if (ws_bytes == 0) { set_error("%s: bad frame size %dx%d", fn, width, height); return RT_ERR_INVALID_ARG; }
     rt_denoise_params q;
     rt_denoise_default_params(&q);
     if (params) q = *params;
-    if (int rc = check_denoise_params(&q, "rt_denoise_device")) return rc;
-    if ((((uintptr_t)d_hits | (uintptr_t)d_workspace) & 15u) ||
-        (((uintptr_t)d_radiance | (uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
-        set_error("rt_denoise_device: d_hits and d_workspace must be 16-byte aligned, the other buffers 4-byte");
+    if (int rc = check_denoise_params(&q, fn)) return rc;
+    if ((((uintptr_t)d_hits | (uintptr_t)d_workspace) & 15u) || ((uintptr_t)d_in & (history ? 15u : 3u)) ||
+        (((uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
+        set_error(history ? "%s: d_hist, d_hits and d_workspace must be 16-byte aligned, the other buffers 4-byte"
+                          : "%s: d_hits and d_workspace must be 16-byte aligned, the other buffers 4-byte", fn);
         return RT_ERR_INVALID_ARG;
     }
     const size_t px = (size_t)width * (size_t)height;
     const struct { const void* p; size_t n; const char* name; } in[3] = {
-        {d_radiance, px * 12, "d_radiance"}, {d_hits, px * 32, "d_hits"}, {d_workspace, ws_bytes, "d_workspace"}};
+        {d_in, px * (history ? 16 : 12), history ? "d_hist" : "d_radiance"}, {d_hits, px * 32, "d_hits"},
+        {d_workspace, ws_bytes, "d_workspace"}};
     const struct { const void* p; size_t n; const char* name; } out[2] = {
         {d_out_rgba, px * 4, "d_out_rgba"}, {d_out_radiance, px * 12, "d_out_radiance"}};
     for (const auto& o : out) {
         if (!o.p) continue;
         for (const auto& i : in)
             if (ranges_overlap(o.p, o.n, i.p, i.n)) {
-                set_error("rt_denoise_device: %s overlaps %s", o.name, i.name);
+                set_error("%s: %s overlaps %s", fn, o.name, i.name);
                 return RT_ERR_INVALID_ARG;
             }
     }
     if (d_out_rgba && d_out_radiance && ranges_overlap(out[0].p, out[0].n, out[1].p, out[1].n)) {
-        set_error("rt_denoise_device: d_out_rgba overlaps d_out_radiance");
+        set_error("%s: d_out_rgba overlaps d_out_radiance", fn);
         return RT_ERR_INVALID_ARG;
     }
     for (int k = 0; k < 2; ++k)
         if (ranges_overlap(in[2].p, in[2].n, in[k].p, in[k].n)) {
-            set_error("rt_denoise_device: d_workspace overlaps %s", in[k].name);
+            set_error("%s: d_workspace overlaps %s", fn, in[k].name);
             return RT_ERR_INVALID_ARG;
         }
     PerDevice& p = ctx->dev[0];
@@ -1818,7 +1822,7 @@ int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radianc
     hipStream_t s = static_cast<hipStream_t>(stream);
     DenoiseArgs d;
     d.width = width; d.height = height;
-    d.radiance = d_radiance;
+    d.radiance = history ? nullptr : static_cast<const float*>(d_in);
     d.hits = reinterpret_cast<const float4*>(d_hits);
     d.workspace = static_cast<float4*>(d_workspace);
     d.out_rgba = static_cast<uchar4*>(d_out_rgba);
@@ -1830,7 +1834,7 @@ int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radianc
     d.form = ctx->denoise_kernel;
     d.only_pass = ctx->denoise_pass < q.iterations ? ctx->denoise_pass : -1;
     if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
-    RT_HIP_CHECK(launch_denoise(d, s));
+    RT_HIP_CHECK(history ? launch_denoise_history(d, static_cast<const float4*>(d_in), s) : launch_denoise(d, s));
     if (ms) {
         RT_HIP_CHECK(hipEventRecord(p.ev1, s));
         RT_HIP_CHECK(hipEventSynchronize(p.ev1));
@@ -1839,6 +1843,20 @@ int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radianc
         *ms = (double)t;
     }
     return RT_OK;
+}
+
+int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radiance, const rt_hit* d_hits,
+                      const rt_denoise_params* params, void* d_workspace, void* d_out_rgba, float* d_out_radiance,
+                      void* stream, double* ms) {
+    return denoise_device("rt_denoise_device", false, ctx, width, height, d_radiance, d_hits, params, d_workspace,
+                          d_out_rgba, d_out_radiance, stream, ms);
+}
+
+int rt_denoise_history_device(rt_ctx* ctx, int width, int height, const void* d_hist, const rt_hit* d_hits,
+                              const rt_denoise_params* params, void* d_workspace, void* d_out_rgba,
+                              float* d_out_radiance, void* stream, double* ms) {
+    return denoise_device("rt_denoise_history_device", true, ctx, width, height, d_hist, d_hits, params, d_workspace,
+                          d_out_rgba, d_out_radiance, stream, ms);
 }
 
 int rt_render_denoised(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
@@ -1998,34 +2016,37 @@ int rt_temporal_device(rt_ctx* ctx, int width, int height, const rt_camera_ubo* 
     return RT_OK;
 }
 
-int rt_render_temporal(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
-                       const rt_temporal_params* tparams, const rt_denoise_params* dparams, uint32_t flags,
-                       uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
-    int rc = check_render_args(ctx, cam, width, height, max_bounces, "rt_render_temporal");
+// rt_render_temporal (adaptive false: dparams null = no filter, else rt_denoise_device on the temporal
+// radiance) and rt_render_temporal_adaptive (rt_denoise_history_device on the new history record, always).
+static int render_temporal(const char* fn, bool adaptive, rt_ctx* ctx, const rt_camera_ubo* cam, int width,
+                           int height, int max_bounces, const rt_temporal_params* tparams,
+                           const rt_denoise_params* dparams, uint32_t flags, uint8_t* out_rgba, float* out_radiance,
+                           rt_stats* stats) {
+    int rc = check_render_args(ctx, cam, width, height, max_bounces, fn);
     if (rc) return rc;
-    if (!out_rgba) { set_error("rt_render_temporal: out_rgba is required"); return RT_ERR_INVALID_ARG; }
+    if (!out_rgba) { set_error("%s: out_rgba is required", fn); return RT_ERR_INVALID_ARG; }
     if (flags & ~(uint32_t)(RT_TEMPORAL_RESET | RT_TEMPORAL_FIXED_SEED)) {
-        set_error("rt_render_temporal: unknown flags 0x%x", flags);
+        set_error("%s: unknown flags 0x%x", fn, flags);
         return RT_ERR_INVALID_ARG;
     }
     if (ctx->dev.size() != 1) {
-        set_error("rt_render_temporal: the context has %zu devices; the history belongs to whole frames of one device",
-                  ctx->dev.size());
+        set_error("%s: the context has %zu devices; the history belongs to whole frames of one device",
+                  fn, ctx->dev.size());
         return RT_ERR_INVALID_ARG;
     }
     PerDevice& p = ctx->dev[0];
     if ((ctx->ext & kExtSpheres) && p.n_spheres > 0) {
-        set_error("rt_render_temporal: spheres are active (extensions bit 8); the hit buffer sees triangles only");
+        set_error("%s: spheres are active (extensions bit 8); the hit buffer sees triangles only", fn);
         return RT_ERR_INVALID_ARG;
     }
     if (ctx->ext & kExtAccumulate) {
-        set_error("rt_render_temporal: extensions bit 4 (accumulation) is set; the frame would be averaged twice");
+        set_error("%s: extensions bit 4 (accumulation) is set; the frame would be averaged twice", fn);
         return RT_ERR_INVALID_ARG;
     }
     if (tparams)
-        if (int rq = check_temporal_params(tparams, "rt_render_temporal")) return rq;
+        if (int rq = check_temporal_params(tparams, fn)) return rq;
     if (dparams)
-        if (int rq = check_denoise_params(dparams, "rt_render_temporal")) return rq;
+        if (int rq = check_denoise_params(dparams, fn)) return rq;
     RT_HIP_CHECK(hipSetDevice(p.device));
     // per pixel: radiance (12 B), two histories (16 B each), two hit buffers (32 B each), the temporal
     // radiance (12 B), RGBA8 (4 B); with a filter its workspace (32 B) and radiance (12 B) behind them.
@@ -2034,13 +2055,13 @@ int rt_render_temporal(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int hei
     const auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
     const size_t o_hist = up(px * 12), o_hits = o_hist + 2 * up(px * 16), o_trad = o_hits + 2 * up(px * 32),
                  o_rgba = o_trad + up(px * 12), o_ws = o_rgba + up(px * 4), o_frad = o_ws + up(px * 32),
-                 total = dparams ? o_frad + up(px * 12) : o_ws;
+                 total = (dparams || adaptive) ? o_frad + up(px * 12) : o_ws;
     if ((flags & RT_TEMPORAL_RESET) || width != p.temporal_w || height != p.temporal_h) p.temporal_valid = false;
     if (total > p.temporal_cap) {
         char* grown = nullptr;
         const hipError_t e = hipMalloc(&grown, total);
         if (e != hipSuccess) {
-            set_error("rt_render_temporal: %zu bytes of frame buffers: %s", total, hipGetErrorString(e));
+            set_error("%s: %zu bytes of frame buffers: %s", fn, total, hipGetErrorString(e));
             return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
         }
         if (p.d_temporal) {
@@ -2068,19 +2089,23 @@ int rt_render_temporal(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int hei
     if (rc) return rc;
     rc = rt_render_hits_device(ctx, cam, width, height, 0, 0, width, height, 0, d_hits[cur], p.stream, nullptr);
     if (rc) return rc;
-    const bool filter = dparams != nullptr;
+    const bool filter = adaptive || dparams != nullptr;
     double t_ms = 0.0, dn_ms = 0.0;
     p.temporal_valid = false;                    // (a failure below leaves no half-written history behind)
     rc = rt_temporal_device(ctx, width, height, cam, d_rad, d_hits[cur], hist ? &p.temporal_cam : nullptr,
                             hist ? d_hist[prev] : nullptr, hist ? d_hits[prev] : nullptr, tparams, d_hist[cur],
-                            filter ? nullptr : base + o_rgba, (filter || out_radiance) ? d_trad : nullptr, p.stream,
+                            filter ? nullptr : base + o_rgba,
+                            ((filter && !adaptive) || (!filter && out_radiance)) ? d_trad : nullptr, p.stream,
                             stats ? &t_ms : nullptr);
     if (rc) return rc;
     const float* d_final_rad = d_trad;
     if (filter) {
         float* d_frad = reinterpret_cast<float*>(base + o_frad);
-        rc = rt_denoise_device(ctx, width, height, d_trad, d_hits[cur], dparams, base + o_ws, base + o_rgba,
-                               out_radiance ? d_frad : nullptr, p.stream, stats ? &dn_ms : nullptr);
+        rc = adaptive ? rt_denoise_history_device(ctx, width, height, d_hist[cur], d_hits[cur], dparams, base + o_ws,
+                                                  base + o_rgba, out_radiance ? d_frad : nullptr, p.stream,
+                                                  stats ? &dn_ms : nullptr)
+                      : rt_denoise_device(ctx, width, height, d_trad, d_hits[cur], dparams, base + o_ws, base + o_rgba,
+                                          out_radiance ? d_frad : nullptr, p.stream, stats ? &dn_ms : nullptr);
         if (rc) return rc;
         d_final_rad = d_frad;
     }
@@ -2094,6 +2119,20 @@ int rt_render_temporal(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int hei
     p.temporal_w = width; p.temporal_h = height;
     p.temporal_cam = *cam;
     return RT_OK;
+}
+
+int rt_render_temporal(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                       const rt_temporal_params* tparams, const rt_denoise_params* dparams, uint32_t flags,
+                       uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
+    return render_temporal("rt_render_temporal", false, ctx, cam, width, height, max_bounces, tparams, dparams, flags,
+                           out_rgba, out_radiance, stats);
+}
+
+int rt_render_temporal_adaptive(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                                const rt_temporal_params* tparams, const rt_denoise_params* dparams, uint32_t flags,
+                                uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
+    return render_temporal("rt_render_temporal_adaptive", true, ctx, cam, width, height, max_bounces, tparams, dparams,
+                           flags, out_rgba, out_radiance, stats);
 }
 
 int rt_band_rows(int height, int band_h, int band_stride, int band_off) {

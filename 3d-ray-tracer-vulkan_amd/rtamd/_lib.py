@@ -41,12 +41,14 @@ EXPORTED = (
     "rt_query_rays_device", "rt_query_rays", "rt_render_hits_device", "rt_pick", "rt_build_scene_map",
     "rt_denoise_default_params", "rt_denoise_workspace_bytes", "rt_denoise_device", "rt_render_denoised",
     "rt_temporal_default_params", "rt_temporal_camera_basis", "rt_temporal_device", "rt_render_temporal",
+    "rt_denoise_history_device", "rt_render_temporal_adaptive",
 )
 
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
 # "src=" field is the first 16 hex digits of SHA-256 over them concatenated.
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
-                 "csrc/rt_denoise.hip", "csrc/rt_temporal.hip", "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h",
+                 "csrc/rt_denoise.hip", "csrc/rt_denoise_history.hip", "csrc/rt_temporal.hip", "csrc/scene_build.cpp",
+                 "csrc/accel_build.cpp", "csrc/rt_internal.h",
                  "csrc/accel_build.h", "../include/rtamd.h")
 
 
@@ -229,6 +231,9 @@ def lib() -> C.CDLL:
                                              C.POINTER(TemporalParams), vp, vp, vp, vp, dp]),
                 "rt_render_temporal": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, C.POINTER(TemporalParams),
                                              C.POINTER(DenoiseParams), C.c_uint32, vp, vp, C.POINTER(Stats)]),
+                "rt_denoise_history_device": (i32, [vp, i32, i32, vp, vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, dp]),
+                "rt_render_temporal_adaptive": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, C.POINTER(TemporalParams),
+                                                      C.POINTER(DenoiseParams), C.c_uint32, vp, vp, C.POINTER(Stats)]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)

@@ -268,6 +268,23 @@ class Renderer:
                                        C.byref(st) if st is not None else None))
         return rgba, rad, (st.as_dict() if st is not None else None)
 
+    def denoise_history_device(self, width: int, height: int, d_hist: int, d_hits: int, d_workspace: int,
+                               d_out_rgba: Optional[int] = None, d_out_radiance: Optional[int] = None,
+                               params: Optional[DenoiseParams] = None, stream: Optional[int] = None,
+                               ms: bool = False):
+        """Enqueue the history-adaptive filter of one whole frame between
+        device buffers (raw device pointers; rt_denoise_history_device,
+        DESIGN.md §4i) on a HIP stream handle: d_hist is a history buffer as
+        temporal_device writes it (never written), the workspace is
+        denoise_workspace_bytes bytes.  Asynchronous unless ms, which waits and
+        returns the passes' device time in milliseconds."""
+        t = C.c_double() if ms else None
+        check(lib().rt_denoise_history_device(self._ctx, width, height, d_hist, d_hits,
+                                              C.byref(params) if params is not None else None, d_workspace,
+                                              d_out_rgba, d_out_radiance, stream,
+                                              C.byref(t) if t is not None else None))
+        return t.value if t is not None else None
+
     # --- temporal accumulation (include/rtamd.h "temporal", DESIGN.md §4h) ---
     def temporal_device(self, width: int, height: int, camera, d_radiance: int, d_hits: int, d_hist_out: int,
                         prev_camera=None, d_hist_prev: Optional[int] = None, d_hits_prev: Optional[int] = None,
@@ -314,23 +331,27 @@ class Renderer:
 
     def render_temporal(self, camera, width: int, height: int, max_bounces: int = REFERENCE_MAX_BOUNCES,
                         params: Optional[TemporalParams] = None, denoise: Optional[DenoiseParams] = None,
-                        reset: bool = False, fixed_seed: bool = False, radiance: bool = False, stats: bool = False):
+                        reset: bool = False, fixed_seed: bool = False, radiance: bool = False, stats: bool = False,
+                        adaptive: bool = False):
         """One frame of a temporally accumulated sequence (rt_render_temporal):
         render with a new sample per camera.frame_count (fixed_seed: the
         context's extensions as they are), first-hit buffer, reprojection of
         the context's history of the previous call, and with `denoise` the
-        spatial filter after it.  reset drops the history first.  Returns
+        spatial filter after it.  adaptive: the history-adaptive filter runs on
+        the new history record instead (rt_render_temporal_adaptive; `denoise`
+        None = its defaults); the two kinds of call share one history.  reset
+        drops the history first.  Returns
         (rgba, radiance or None, stats dict or None); ms = render + temporal
         (+ filter).  One device, no active spheres, extensions bit 4 off."""
         rgba = np.empty((height, width, 4), dtype=np.uint8)
         rad = np.empty((height, width, 3), dtype=np.float32) if radiance else None
         st = Stats() if stats else None
         flags = (RT_TEMPORAL_RESET if reset else 0) | (RT_TEMPORAL_FIXED_SEED if fixed_seed else 0)
-        check(lib().rt_render_temporal(self._ctx, C.byref(_ubo(camera)), width, height, max_bounces,
-                                       C.byref(params) if params is not None else None,
-                                       C.byref(denoise) if denoise is not None else None, flags, rgba.ctypes.data,
-                                       rad.ctypes.data if rad is not None else None,
-                                       C.byref(st) if st is not None else None))
+        call = lib().rt_render_temporal_adaptive if adaptive else lib().rt_render_temporal
+        check(call(self._ctx, C.byref(_ubo(camera)), width, height, max_bounces,
+                   C.byref(params) if params is not None else None,
+                   C.byref(denoise) if denoise is not None else None, flags, rgba.ctypes.data,
+                   rad.ctypes.data if rad is not None else None, C.byref(st) if st is not None else None))
         return rgba, rad, (st.as_dict() if st is not None else None)
 
 
@@ -391,7 +412,7 @@ class HipEngine:
                  height: int = REFERENCE_HEIGHT, max_bounces: int = REFERENCE_MAX_BOUNCES,
                  device_ids: Sequence[int] = (0,), collect_stats: bool = False, pipelined: bool = True,
                  inflight: int = 4, denoise: Optional[DenoiseParams] = None,
-                 temporal: Optional[TemporalParams] = None):
+                 temporal: Optional[TemporalParams] = None, adaptive: bool = False):
         self.frame_queue = frame_queue
         # pipelined: `inflight` frames in flight (rt_render_async, one slot and
         # trace stream each), so the frames' traces overlap each other and
@@ -401,10 +422,13 @@ class HipEngine:
         # temporal: every frame goes through render_temporal (synchronous as well), frame k of the
         # engine with frame_count k, so that every frame is a new sample; with denoise too, the
         # filter runs after the accumulation.
+        # adaptive: the temporal path with the history-adaptive filter (render_temporal's adaptive=;
+        # temporal None = the default parameters, denoise = the filter's parameters or None for its defaults).
         self.denoise = denoise
-        self.temporal = temporal
+        self.temporal = TemporalParams() if adaptive and temporal is None else temporal
+        self.adaptive = bool(adaptive)
         self.temporal_frames = 0
-        self.pipelined = pipelined and not collect_stats and denoise is None and temporal is None
+        self.pipelined = pipelined and not collect_stats and denoise is None and self.temporal is None
         self.inflight = max(1, min(8, int(inflight)))
         self.width, self.height, self.max_bounces = width, height, max_bounces
         self.device_ids = tuple(device_ids)
@@ -473,7 +497,8 @@ class HipEngine:
                     if self.temporal is not None:
                         ubo.frame_count = self.temporal_frames
                         rgba, _, st = renderer.render_temporal(ubo, self.width, self.height, self.max_bounces,
-                                                               self.temporal, self.denoise, stats=self.collect_stats)
+                                                               self.temporal, self.denoise, stats=self.collect_stats,
+                                                               adaptive=self.adaptive)
                         self.temporal_frames += 1
                     elif self.denoise is not None:
                         rgba, _, st = renderer.render_denoised(ubo, self.width, self.height, self.max_bounces,

@@ -454,6 +454,53 @@ int rt_render_temporal(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int hei
                        const rt_temporal_params* tparams, const rt_denoise_params* dparams, uint32_t flags,
                        uint8_t* out_rgba, float* out_radiance, rt_stats* stats);
 
+/* ------------------------------------------------------- adaptive denoise -- */
+/* NON-REFERENCE: the a-trous filter for an accumulated frame, wide where the
+ * history is short and out of the way where it is long.  It reads a history
+ * buffer (c.rgb linear, n) as rt_temporal_device writes it and the same
+ * frame's hit records, and is rt_denoise_device's filter with n in three
+ * places.  A pixel is live with tri >= 0 and n >= 1 (a NaN n fails); only live
+ * pixels are filtered and only live pixels are taps.  A live pixel is filtered
+ * in the first max(0, iterations - floor(log2 n)) passes (n = 1: all of them,
+ * n = 2..3: one fewer, n >= 2^iterations: none) and keeps its colour bit for
+ * bit in the others, still serving as a tap.  Its luminance term is y = the
+ * luminance difference * ((2^i / sigma_color) * n_p): the tolerance tightens
+ * with the history.  A tap's weight is multiplied by n_q: it counts by its
+ * samples.  With n = 1 on every hit pixel and c = g * g the result is
+ * rt_denoise_device(g) bit for bit; with n >= 2^iterations everywhere it is
+ * sqrt(c).  The contract, operation by operation in IEEE binary32, is
+ * DESIGN.md §4i (tests/denoise_history_ref.py restates it in numpy, bit for
+ * bit).  Added at ABI version 6 without a bump: no existing struct or argument
+ * list changed.
+ *
+ * One whole width x height frame on device 0 of ctx, between DEVICE buffers:
+ * d_hist (width*height records of 4 floats, 16-byte aligned, never written)
+ * and d_hits (16-byte aligned) in; d_out_rgba and / or d_out_radiance out, as
+ * rt_denoise_device's; d_workspace: rt_denoise_workspace_bytes bytes, 16-byte
+ * aligned, left as scratch.  params NULL = the defaults; same fields and
+ * ranges.  Stream and ms as rt_denoise_device.  Allocates nothing and touches
+ * no render, query or temporal state ("plain_kernels" included).  The outputs
+ * must not overlap the inputs, the workspace or each other.
+ * RT_ERR_INVALID_ARG: a null input, both outputs null, a bad size or
+ * parameter, a misaligned buffer, an overlap.  Options "denoise_kernel" and
+ * "denoise_pass" apply to it as they do to rt_denoise_device. */
+int rt_denoise_history_device(rt_ctx* ctx, int width, int height, const void* d_hist, const rt_hit* d_hits,
+                              const rt_denoise_params* params, void* d_workspace,
+                              void* d_out_rgba, float* d_out_radiance, void* stream, double* ms);
+/* rt_render_temporal with the adaptive filter always on: the frame is rendered
+ * and blended into the context's history exactly as rt_render_temporal does it
+ * (rt_temporal_device with both optional outputs NULL), then
+ * rt_denoise_history_device filters the new history record with the current
+ * hit records into the outputs.  dparams NULL = the defaults.  The history,
+ * the hit buffers and the camera are the state rt_render_temporal uses, so
+ * calls to the two may be mixed within one sequence; the history keeps the
+ * unfiltered accumulation.  Same flags, same refusals and same history-drop
+ * rules as rt_render_temporal.  stats (nullable): the render's counters, ms =
+ * the render's device time + the temporal kernel's + the filter's. */
+int rt_render_temporal_adaptive(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                                const rt_temporal_params* tparams, const rt_denoise_params* dparams, uint32_t flags,
+                                uint8_t* out_rgba, float* out_radiance, rt_stats* stats);
+
 /* Schedule options (no effect on results, which are identical for every
  * setting):
  *   "kernel"        0 only: the one kernel, one lane per pixel (the
@@ -648,11 +695,15 @@ int rt_render_temporal(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int hei
  *                   workgroup per 32x8 pixels of one residue class, the halo
  *                   tile in LDS), 0 (default) = per step size the form
  *                   measured faster.  Same results; 1 and 2
- *                   are for tests and tools/denoise_bench.py
+ *                   are for tests and tools/denoise_bench.py.  Applies to
+ *                   rt_denoise_history_device's passes in the same way (its
+ *                   own two forms and its own table, DESIGN.md §4i;
+ *                   tools/adaptive_bench.py)
  *   "denoise_pass"  rt_denoise_device: i in 0..5 = only pass i is enqueued, on
  *                   whatever an earlier call left in the workspace
  *                   (tools/denoise_bench.py times a pass this way; the output
- *                   is meaningless); -1 (default) = every pass
+ *                   is meaningless); -1 (default) = every pass.  The same for
+ *                   rt_denoise_history_device
  *   "temporal_tile" rt_temporal_device's lane mapping: 1 = a wave on 64
  *                   consecutive pixels of a row, 2 = a wave on a 16x4 tile,
  *                   0 (default) = the one measured faster.
