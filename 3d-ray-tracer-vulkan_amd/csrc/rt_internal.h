@@ -311,4 +311,25 @@ struct TemporalArgs {
 };
 hipError_t launch_temporal(const TemporalArgs& t, hipStream_t stream);
 
+// rt_variance.hip: the accumulation with luminance moments and the
+// variance-guided filter (rtamd.h rt_temporal_moments_device and
+// rt_denoise_variance_device), enqueued on `stream`; validated
+// arguments, nothing allocated.  mom_prev is null exactly when t.hist_prev is.
+hipError_t launch_temporal_moments(const TemporalArgs& t, const float2* mom_prev, float2* mom_out, hipStream_t stream);
+struct VarianceArgs {
+    int           width, height;
+    const float4* hist;         // (c.rgb, n) per pixel
+    const float2* mom;          // (m1, m2) per pixel
+    const float4* hits;         // rt_hit records, 2 float4 per pixel
+    float4*       workspace;    // 2 x width x height float4: records (c.rgb, v)
+    uchar4*       out_rgba;     // nullable
+    float*        out_rad;      // nullable
+    int           iterations, normal_power_log2, min_history;
+    float         sigma_depth, sigma_lum;
+    int           form;         // option denoise_kernel: 0 = the measured choice at step 1, 1 = plain, 2 = tiled at step 1
+    int           only_pass;    // option denoise_pass: -1 = the estimate and every pass, i = pass i alone (timing)
+    int           stage;        // option variance_stage: -1 = everything, 0 = the estimate alone (timing)
+};
+hipError_t launch_denoise_variance(const VarianceArgs& d, hipStream_t stream);
+
 }  // namespace rtamd

@@ -326,6 +326,9 @@ struct PerDevice {
     bool         temporal_valid = false;
     int          temporal_last = 0, temporal_w = 0, temporal_h = 0;
     rt_camera_ubo temporal_cam = {};
+    // rt_render_temporal_variance: the pair of moments buffers behind the other parts of d_temporal holds,
+    // at index temporal_last, the moments of the current history (false after a call that wrote none)
+    bool         moments_valid = false;
 };
 
 static constexpr size_t kMaxOrders = 16;
@@ -434,6 +437,7 @@ struct rt_ctx {
     int  denoise_pass = -1;        // rt_denoise_device: i >= 0 = enqueue pass i alone (tools/denoise_bench.py)
     int  temporal_tile = 0;        // rt_temporal_device: 0 = the lane mapping measured faster, 1 = a wave on 64
                                    //   pixels of a row, 2 = on a 16x4 tile (rt_temporal.hip; same results)
+    int  variance_stage = -1;      // rt_denoise_variance_device: 0 = enqueue the estimate alone (tools/variance_bench.py)
     int  split_bounce = 0;         // accel walk: paths alive at this bounce finish in a second kernel
                                    //   (0 = one kernel)
     // At the next upload: 0 = the reference's tree and order; 1 / 8 = the
@@ -1859,6 +1863,101 @@ int rt_denoise_history_device(rt_ctx* ctx, int width, int height, const void* d_
                           d_out_rgba, d_out_radiance, stream, ms);
 }
 
+static int check_variance_params(const rt_variance_params* q, const char* fn) {
+    if (q->iterations < 1 || q->iterations > 6 || q->normal_power_log2 < 0 || q->normal_power_log2 > 10) {
+        set_error("%s: iterations must be in [1, 6] and normal_power_log2 in [0, 10], got %d and %d", fn,
+                  q->iterations, q->normal_power_log2);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite(q->sigma_depth) || !std::isfinite(q->sigma_lum) || !(q->sigma_depth > 0.0f) ||
+        !(q->sigma_lum > 0.0f)) {
+        set_error("%s: sigma_depth and sigma_lum must be finite and > 0, got %g and %g", fn, (double)q->sigma_depth,
+                  (double)q->sigma_lum);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (q->min_history < 1 || q->min_history > 1024) {
+        set_error("%s: min_history must be in [1, 1024], got %d", fn, q->min_history);
+        return RT_ERR_INVALID_ARG;
+    }
+    return RT_OK;
+}
+
+// rt_denoise_history_device's checks with the moments as a third read-only input.
+int rt_denoise_variance_device(rt_ctx* ctx, int width, int height, const void* d_hist, const void* d_mom,
+                               const rt_hit* d_hits, const rt_variance_params* params, void* d_workspace,
+                               void* d_out_rgba, float* d_out_radiance, void* stream, double* ms) {
+    const char* const fn = "rt_denoise_variance_device";
+    if (!ctx || !d_hist || !d_mom || !d_hits || !d_workspace) {
+        set_error("%s: null context or buffer", fn);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (!d_out_rgba && !d_out_radiance) { set_error("%s: both outputs are null", fn); return RT_ERR_INVALID_ARG; }
+    const size_t ws_bytes = rt_denoise_workspace_bytes(width, height);
+    if (ws_bytes == 0) { set_error("%s: bad frame size %dx%d", fn, width, height); return RT_ERR_INVALID_ARG; }
+    rt_variance_params q;
+    rt_variance_default_params(&q);
+    if (params) q = *params;
+    if (int rc = check_variance_params(&q, fn)) return rc;
+    if ((((uintptr_t)d_hits | (uintptr_t)d_workspace | (uintptr_t)d_hist) & 15u) || ((uintptr_t)d_mom & 7u) ||
+        (((uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
+        set_error("%s: d_hist, d_hits and d_workspace must be 16-byte aligned, d_mom 8-byte, the other buffers 4-byte",
+                  fn);
+        return RT_ERR_INVALID_ARG;
+    }
+    const size_t px = (size_t)width * (size_t)height;
+    const struct { const void* p; size_t n; const char* name; } in[4] = {
+        {d_hist, px * 16, "d_hist"}, {d_mom, px * 8, "d_mom"}, {d_hits, px * 32, "d_hits"},
+        {d_workspace, ws_bytes, "d_workspace"}};
+    const struct { const void* p; size_t n; const char* name; } out[2] = {
+        {d_out_rgba, px * 4, "d_out_rgba"}, {d_out_radiance, px * 12, "d_out_radiance"}};
+    for (const auto& o : out) {
+        if (!o.p) continue;
+        for (const auto& i : in)
+            if (ranges_overlap(o.p, o.n, i.p, i.n)) {
+                set_error("%s: %s overlaps %s", fn, o.name, i.name);
+                return RT_ERR_INVALID_ARG;
+            }
+    }
+    if (d_out_rgba && d_out_radiance && ranges_overlap(out[0].p, out[0].n, out[1].p, out[1].n)) {
+        set_error("%s: d_out_rgba overlaps d_out_radiance", fn);
+        return RT_ERR_INVALID_ARG;
+    }
+    for (int k = 0; k < 3; ++k)
+        if (ranges_overlap(in[3].p, in[3].n, in[k].p, in[k].n)) {
+            set_error("%s: d_workspace overlaps %s", fn, in[k].name);
+            return RT_ERR_INVALID_ARG;
+        }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    VarianceArgs d;
+    d.width = width; d.height = height;
+    d.hist = static_cast<const float4*>(d_hist);
+    d.mom = static_cast<const float2*>(d_mom);
+    d.hits = reinterpret_cast<const float4*>(d_hits);
+    d.workspace = static_cast<float4*>(d_workspace);
+    d.out_rgba = static_cast<uchar4*>(d_out_rgba);
+    d.out_rad = d_out_radiance;
+    d.iterations = q.iterations;
+    d.normal_power_log2 = q.normal_power_log2;
+    d.min_history = q.min_history;
+    d.sigma_depth = q.sigma_depth;
+    d.sigma_lum = q.sigma_lum;
+    d.form = ctx->denoise_kernel;
+    d.only_pass = ctx->denoise_pass < q.iterations ? ctx->denoise_pass : -1;
+    d.stage = ctx->variance_stage;
+    if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
+    RT_HIP_CHECK(launch_denoise_variance(d, s));
+    if (ms) {
+        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
+        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
+        float t = 0.0f;
+        RT_HIP_CHECK(hipEventElapsedTime(&t, p.ev0, p.ev1));
+        *ms = (double)t;
+    }
+    return RT_OK;
+}
+
 int rt_render_denoised(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
                        const rt_denoise_params* params, uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
     int rc = check_render_args(ctx, cam, width, height, max_bounces, "rt_render_denoised");
@@ -1941,48 +2040,59 @@ static TemporalBasis temporal_basis_of(const rt_camera_ubo* cam) {
     return TemporalBasis{b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], b[9], b[10], b[11], b[12]};
 }
 
-int rt_temporal_device(rt_ctx* ctx, int width, int height, const rt_camera_ubo* cam, const float* d_radiance,
-                       const rt_hit* d_hits, const rt_camera_ubo* prev_cam, const void* d_hist_prev,
-                       const rt_hit* d_hits_prev, const rt_temporal_params* params, void* d_hist_out,
-                       void* d_out_rgba, float* d_out_radiance, void* stream, double* ms) {
-    if (!ctx || !cam || !d_radiance || !d_hits || !d_hist_out) {
-        set_error("rt_temporal_device: null context, camera, input or d_hist_out");
+// rt_temporal_device and (moments true) rt_temporal_moments_device, which adds the two moments buffers:
+// the same checks and timing.
+static int temporal_device(const char* fn, bool moments, rt_ctx* ctx, int width, int height, const rt_camera_ubo* cam,
+                           const float* d_radiance, const rt_hit* d_hits, const rt_camera_ubo* prev_cam,
+                           const void* d_hist_prev, const rt_hit* d_hits_prev, const rt_temporal_params* params,
+                           void* d_hist_out, void* d_out_rgba, float* d_out_radiance, void* stream, double* ms,
+                           const void* d_mom_prev, void* d_mom_out) {
+    if (!ctx || !cam || !d_radiance || !d_hits || !d_hist_out || (moments && !d_mom_out)) {
+        set_error(moments ? "%s: null context, camera, input, d_hist_out or d_mom_out"
+                          : "%s: null context, camera, input or d_hist_out", fn);
         return RT_ERR_INVALID_ARG;
     }
-    const int n_prev = (prev_cam != nullptr) + (d_hist_prev != nullptr) + (d_hits_prev != nullptr);
-    if (n_prev != 0 && n_prev != 3) {
-        set_error("rt_temporal_device: prev_cam, d_hist_prev and d_hits_prev must be all null or all given");
+    const int n_prev = (prev_cam != nullptr) + (d_hist_prev != nullptr) + (d_hits_prev != nullptr) +
+                       (d_mom_prev != nullptr);
+    if (n_prev != 0 && n_prev != (moments ? 4 : 3)) {
+        set_error(moments ? "%s: prev_cam, d_hist_prev, d_hits_prev and d_mom_prev must be all null or all given"
+                          : "%s: prev_cam, d_hist_prev and d_hits_prev must be all null or all given", fn);
         return RT_ERR_INVALID_ARG;
     }
     if (rt_denoise_workspace_bytes(width, height) == 0) {
-        set_error("rt_temporal_device: bad frame size %dx%d", width, height);
+        set_error("%s: bad frame size %dx%d", fn, width, height);
         return RT_ERR_INVALID_ARG;
     }
     rt_temporal_params q;
     rt_temporal_default_params(&q);
     if (params) q = *params;
-    if (int rc = check_temporal_params(&q, "rt_temporal_device")) return rc;
+    if (int rc = check_temporal_params(&q, fn)) return rc;
     if ((((uintptr_t)d_hits | (uintptr_t)d_hits_prev | (uintptr_t)d_hist_prev | (uintptr_t)d_hist_out) & 15u) ||
         (((uintptr_t)d_radiance | (uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
-        set_error("rt_temporal_device: the hit and history buffers must be 16-byte aligned, the other buffers 4-byte");
+        set_error("%s: the hit and history buffers must be 16-byte aligned, the other buffers 4-byte", fn);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)d_mom_prev | (uintptr_t)d_mom_out) & 7u) {
+        set_error("%s: the moments buffers must be 8-byte aligned", fn);
         return RT_ERR_INVALID_ARG;
     }
     const size_t px = (size_t)width * (size_t)height;
     struct Range { const void* p; size_t n; const char* name; };
-    const Range in[4] = {{d_radiance, px * 12, "d_radiance"}, {d_hits, px * 32, "d_hits"},
-                         {d_hist_prev, px * 16, "d_hist_prev"}, {d_hits_prev, px * 32, "d_hits_prev"}};
-    const Range out[3] = {{d_hist_out, px * 16, "d_hist_out"}, {d_out_rgba, px * 4, "d_out_rgba"},
-                          {d_out_radiance, px * 12, "d_out_radiance"}};
-    for (int o = 0; o < 3; ++o) {
+    const Range in[5] = {{d_radiance, px * 12, "d_radiance"}, {d_hits, px * 32, "d_hits"},
+                         {d_hist_prev, px * 16, "d_hist_prev"}, {d_hits_prev, px * 32, "d_hits_prev"},
+                         {d_mom_prev, px * 8, "d_mom_prev"}};
+    const Range out[4] = {{d_hist_out, px * 16, "d_hist_out"}, {d_out_rgba, px * 4, "d_out_rgba"},
+                          {d_out_radiance, px * 12, "d_out_radiance"}, {d_mom_out, px * 8, "d_mom_out"}};
+    for (int o = 0; o < 4; ++o) {
         if (!out[o].p) continue;
         for (const Range& i : in)
             if (i.p && ranges_overlap(out[o].p, out[o].n, i.p, i.n)) {
-                set_error("rt_temporal_device: %s overlaps %s", out[o].name, i.name);
+                set_error("%s: %s overlaps %s", fn, out[o].name, i.name);
                 return RT_ERR_INVALID_ARG;
             }
         for (int o2 = 0; o2 < o; ++o2)
             if (out[o2].p && ranges_overlap(out[o].p, out[o].n, out[o2].p, out[o2].n)) {
-                set_error("rt_temporal_device: %s overlaps %s", out[o].name, out[o2].name);
+                set_error("%s: %s overlaps %s", fn, out[o].name, out[o2].name);
                 return RT_ERR_INVALID_ARG;
             }
     }
@@ -2005,7 +2115,9 @@ int rt_temporal_device(rt_ctx* ctx, int width, int height, const rt_camera_ubo* 
     t.out_rad = d_out_radiance;
     t.form = ctx->temporal_tile;
     if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
-    RT_HIP_CHECK(launch_temporal(t, s));
+    RT_HIP_CHECK(moments ? launch_temporal_moments(t, static_cast<const float2*>(d_mom_prev),
+                                                   static_cast<float2*>(d_mom_out), s)
+                         : launch_temporal(t, s));
     if (ms) {
         RT_HIP_CHECK(hipEventRecord(p.ev1, s));
         RT_HIP_CHECK(hipEventSynchronize(p.ev1));
@@ -2016,12 +2128,33 @@ int rt_temporal_device(rt_ctx* ctx, int width, int height, const rt_camera_ubo* 
     return RT_OK;
 }
 
-// rt_render_temporal (adaptive false: dparams null = no filter, else rt_denoise_device on the temporal
-// radiance) and rt_render_temporal_adaptive (rt_denoise_history_device on the new history record, always).
-static int render_temporal(const char* fn, bool adaptive, rt_ctx* ctx, const rt_camera_ubo* cam, int width,
+int rt_temporal_device(rt_ctx* ctx, int width, int height, const rt_camera_ubo* cam, const float* d_radiance,
+                       const rt_hit* d_hits, const rt_camera_ubo* prev_cam, const void* d_hist_prev,
+                       const rt_hit* d_hits_prev, const rt_temporal_params* params, void* d_hist_out,
+                       void* d_out_rgba, float* d_out_radiance, void* stream, double* ms) {
+    return temporal_device("rt_temporal_device", false, ctx, width, height, cam, d_radiance, d_hits, prev_cam,
+                           d_hist_prev, d_hits_prev, params, d_hist_out, d_out_rgba, d_out_radiance, stream, ms, nullptr,
+                           nullptr);
+}
+
+int rt_temporal_moments_device(rt_ctx* ctx, int width, int height, const rt_camera_ubo* cam, const float* d_radiance,
+                               const rt_hit* d_hits, const rt_camera_ubo* prev_cam, const void* d_hist_prev,
+                               const rt_hit* d_hits_prev, const rt_temporal_params* params, void* d_hist_out,
+                               void* d_out_rgba, float* d_out_radiance, void* stream, double* ms,
+                               const void* d_mom_prev, void* d_mom_out) {
+    return temporal_device("rt_temporal_moments_device", true, ctx, width, height, cam, d_radiance, d_hits, prev_cam,
+                           d_hist_prev, d_hits_prev, params, d_hist_out, d_out_rgba, d_out_radiance, stream, ms,
+                           d_mom_prev, d_mom_out);
+}
+
+// rt_render_temporal (mode 0: dparams null = no filter, else rt_denoise_device on the temporal radiance),
+// rt_render_temporal_adaptive (mode 1: rt_denoise_history_device on the new history record, always) and
+// rt_render_temporal_variance (mode 2: rt_temporal_moments_device, then rt_denoise_variance_device with vparams).
+static int render_temporal(const char* fn, int mode, rt_ctx* ctx, const rt_camera_ubo* cam, int width,
                            int height, int max_bounces, const rt_temporal_params* tparams,
-                           const rt_denoise_params* dparams, uint32_t flags, uint8_t* out_rgba, float* out_radiance,
-                           rt_stats* stats) {
+                           const rt_denoise_params* dparams, const rt_variance_params* vparams, uint32_t flags,
+                           uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
+    const bool adaptive = mode == 1, variance = mode == 2;
     int rc = check_render_args(ctx, cam, width, height, max_bounces, fn);
     if (rc) return rc;
     if (!out_rgba) { set_error("%s: out_rgba is required", fn); return RT_ERR_INVALID_ARG; }
@@ -2047,16 +2180,22 @@ static int render_temporal(const char* fn, bool adaptive, rt_ctx* ctx, const rt_
         if (int rq = check_temporal_params(tparams, fn)) return rq;
     if (dparams)
         if (int rq = check_denoise_params(dparams, fn)) return rq;
+    if (vparams)
+        if (int rq = check_variance_params(vparams, fn)) return rq;
     RT_HIP_CHECK(hipSetDevice(p.device));
     // per pixel: radiance (12 B), two histories (16 B each), two hit buffers (32 B each), the temporal
-    // radiance (12 B), RGBA8 (4 B); with a filter its workspace (32 B) and radiance (12 B) behind them.
+    // radiance (12 B), RGBA8 (4 B); with a filter its workspace (32 B) and radiance (12 B) behind them;
+    // with the variance-guided filter two moments buffers (8 B each) behind those.
     // Each part on a 256-byte boundary.
     const size_t px = (size_t)width * (size_t)height;
     const auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
     const size_t o_hist = up(px * 12), o_hits = o_hist + 2 * up(px * 16), o_trad = o_hits + 2 * up(px * 32),
                  o_rgba = o_trad + up(px * 12), o_ws = o_rgba + up(px * 4), o_frad = o_ws + up(px * 32),
-                 total = (dparams || adaptive) ? o_frad + up(px * 12) : o_ws;
+                 o_mom = o_frad + up(px * 12),
+                 total = variance ? o_mom + 2 * up(px * 8) : ((dparams || adaptive) ? o_mom : o_ws);
     if ((flags & RT_TEMPORAL_RESET) || width != p.temporal_w || height != p.temporal_h) p.temporal_valid = false;
+    // the moments are not those of the history (rt_render_temporal or _adaptive advanced it last): a new sequence
+    if (variance && !p.moments_valid) p.temporal_valid = false;
     if (total > p.temporal_cap) {
         char* grown = nullptr;
         const hipError_t e = hipMalloc(&grown, total);
@@ -2089,19 +2228,33 @@ static int render_temporal(const char* fn, bool adaptive, rt_ctx* ctx, const rt_
     if (rc) return rc;
     rc = rt_render_hits_device(ctx, cam, width, height, 0, 0, width, height, 0, d_hits[cur], p.stream, nullptr);
     if (rc) return rc;
-    const bool filter = adaptive || dparams != nullptr;
+    const bool filter = adaptive || variance || dparams != nullptr;
     double t_ms = 0.0, dn_ms = 0.0;
     p.temporal_valid = false;                    // (a failure below leaves no half-written history behind)
-    rc = rt_temporal_device(ctx, width, height, cam, d_rad, d_hits[cur], hist ? &p.temporal_cam : nullptr,
-                            hist ? d_hist[prev] : nullptr, hist ? d_hits[prev] : nullptr, tparams, d_hist[cur],
-                            filter ? nullptr : base + o_rgba,
-                            ((filter && !adaptive) || (!filter && out_radiance)) ? d_trad : nullptr, p.stream,
-                            stats ? &t_ms : nullptr);
+    p.moments_valid = false;
+    char* d_mom[2] = {nullptr, nullptr};         // (the variance-guided filter's alone)
+    if (variance) {
+        d_mom[0] = base + o_mom;
+        d_mom[1] = base + o_mom + up(px * 8);
+        rc = rt_temporal_moments_device(ctx, width, height, cam, d_rad, d_hits[cur], hist ? &p.temporal_cam : nullptr,
+                                        hist ? d_hist[prev] : nullptr, hist ? d_hits[prev] : nullptr, tparams,
+                                        d_hist[cur], nullptr, nullptr, p.stream, stats ? &t_ms : nullptr,
+                                        hist ? d_mom[prev] : nullptr, d_mom[cur]);
+    } else {
+        rc = rt_temporal_device(ctx, width, height, cam, d_rad, d_hits[cur], hist ? &p.temporal_cam : nullptr,
+                                hist ? d_hist[prev] : nullptr, hist ? d_hits[prev] : nullptr, tparams, d_hist[cur],
+                                filter ? nullptr : base + o_rgba,
+                                ((filter && !adaptive) || (!filter && out_radiance)) ? d_trad : nullptr, p.stream,
+                                stats ? &t_ms : nullptr);
+    }
     if (rc) return rc;
     const float* d_final_rad = d_trad;
     if (filter) {
         float* d_frad = reinterpret_cast<float*>(base + o_frad);
-        rc = adaptive ? rt_denoise_history_device(ctx, width, height, d_hist[cur], d_hits[cur], dparams, base + o_ws,
+        rc = variance ? rt_denoise_variance_device(ctx, width, height, d_hist[cur], d_mom[cur], d_hits[cur], vparams,
+                                                   base + o_ws, base + o_rgba, out_radiance ? d_frad : nullptr,
+                                                   p.stream, stats ? &dn_ms : nullptr)
+           : adaptive ? rt_denoise_history_device(ctx, width, height, d_hist[cur], d_hits[cur], dparams, base + o_ws,
                                                   base + o_rgba, out_radiance ? d_frad : nullptr, p.stream,
                                                   stats ? &dn_ms : nullptr)
                       : rt_denoise_device(ctx, width, height, d_trad, d_hits[cur], dparams, base + o_ws, base + o_rgba,
@@ -2115,6 +2268,7 @@ static int render_temporal(const char* fn, bool adaptive, rt_ctx* ctx, const rt_
         RT_HIP_CHECK(hipMemcpyAsync(out_radiance, d_final_rad, px * 12, hipMemcpyDeviceToHost, p.stream));
     RT_HIP_CHECK(hipStreamSynchronize(p.stream));
     p.temporal_valid = true;
+    p.moments_valid = variance;
     p.temporal_last = cur;
     p.temporal_w = width; p.temporal_h = height;
     p.temporal_cam = *cam;
@@ -2124,15 +2278,22 @@ static int render_temporal(const char* fn, bool adaptive, rt_ctx* ctx, const rt_
 int rt_render_temporal(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
                        const rt_temporal_params* tparams, const rt_denoise_params* dparams, uint32_t flags,
                        uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
-    return render_temporal("rt_render_temporal", false, ctx, cam, width, height, max_bounces, tparams, dparams, flags,
-                           out_rgba, out_radiance, stats);
+    return render_temporal("rt_render_temporal", 0, ctx, cam, width, height, max_bounces, tparams, dparams, nullptr,
+                           flags, out_rgba, out_radiance, stats);
 }
 
 int rt_render_temporal_adaptive(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
                                 const rt_temporal_params* tparams, const rt_denoise_params* dparams, uint32_t flags,
                                 uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
-    return render_temporal("rt_render_temporal_adaptive", true, ctx, cam, width, height, max_bounces, tparams, dparams,
-                           flags, out_rgba, out_radiance, stats);
+    return render_temporal("rt_render_temporal_adaptive", 1, ctx, cam, width, height, max_bounces, tparams, dparams,
+                           nullptr, flags, out_rgba, out_radiance, stats);
+}
+
+int rt_render_temporal_variance(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                                const rt_temporal_params* tparams, const rt_variance_params* vparams, uint32_t flags,
+                                uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
+    return render_temporal("rt_render_temporal_variance", 2, ctx, cam, width, height, max_bounces, tparams, nullptr,
+                           vparams, flags, out_rgba, out_radiance, stats);
 }
 
 int rt_band_rows(int height, int band_h, int band_stride, int band_off) {
@@ -2737,6 +2898,7 @@ static const Option kOptions[] = {
     in_range("denoise_kernel", &rt_ctx::denoise_kernel, 0, 2),
     in_range("denoise_pass", &rt_ctx::denoise_pass, -1, 5),
     in_range("temporal_tile", &rt_ctx::temporal_tile, 0, 2),
+    in_range("variance_stage", &rt_ctx::variance_stage, -1, 0),
 };
 
 static const Option* find_option(const char* name) {

@@ -42,13 +42,15 @@ EXPORTED = (
     "rt_denoise_default_params", "rt_denoise_workspace_bytes", "rt_denoise_device", "rt_render_denoised",
     "rt_temporal_default_params", "rt_temporal_camera_basis", "rt_temporal_device", "rt_render_temporal",
     "rt_denoise_history_device", "rt_render_temporal_adaptive",
+    "rt_temporal_moments_device", "rt_variance_default_params", "rt_denoise_variance_device",
+    "rt_render_temporal_variance",
 )
 
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
 # "src=" field is the first 16 hex digits of SHA-256 over them concatenated.
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
-                 "csrc/rt_denoise.hip", "csrc/rt_denoise_history.hip", "csrc/rt_temporal.hip", "csrc/scene_build.cpp",
-                 "csrc/accel_build.cpp", "csrc/rt_internal.h",
+                 "csrc/rt_denoise.hip", "csrc/rt_denoise_history.hip", "csrc/rt_temporal.hip", "csrc/rt_variance.hip",
+                 "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h",
                  "csrc/accel_build.h", "../include/rtamd.h")
 
 
@@ -138,13 +140,22 @@ class TemporalParams(C.Structure):      # rt_temporal_params; the defaults are r
         super().__init__(max_history, plane_tol, normal_min, 0)
 
 
+class VarianceParams(C.Structure):      # rt_variance_params; the defaults are rt_variance_default_params's
+    _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("sigma_depth", C.c_float),
+                ("sigma_lum", C.c_float), ("min_history", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    def __init__(self, iterations: int = 4, normal_power_log2: int = 7, sigma_depth: float = 0.005,
+                 sigma_lum: float = 1.0, min_history: int = 4):
+        super().__init__(iterations, normal_power_log2, sigma_depth, sigma_lum, min_history)
+
+
 RT_QUERY_ANY = 1
 RT_TEMPORAL_RESET = 1           # rt_render_temporal's flags
 RT_TEMPORAL_FIXED_SEED = 2
 
 assert C.sizeof(CameraUBO) == 80
 assert C.sizeof(Ray) == 32 and C.sizeof(Hit) == 32 and C.sizeof(DenoiseParams) == 16
-assert C.sizeof(TemporalParams) == 16
+assert C.sizeof(TemporalParams) == 16 and C.sizeof(VarianceParams) == 32
 
 _lock = threading.Lock()
 _lib = None
@@ -234,6 +245,13 @@ def lib() -> C.CDLL:
                 "rt_denoise_history_device": (i32, [vp, i32, i32, vp, vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, dp]),
                 "rt_render_temporal_adaptive": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, C.POINTER(TemporalParams),
                                                       C.POINTER(DenoiseParams), C.c_uint32, vp, vp, C.POINTER(Stats)]),
+                "rt_temporal_moments_device": (i32, [vp, i32, i32, C.POINTER(CameraUBO), vp, vp, C.POINTER(CameraUBO), vp,
+                                                     vp, C.POINTER(TemporalParams), vp, vp, vp, vp, dp, vp, vp]),
+                "rt_variance_default_params": (None, [C.POINTER(VarianceParams)]),
+                "rt_denoise_variance_device": (i32, [vp, i32, i32, vp, vp, vp, C.POINTER(VarianceParams), vp, vp, vp, vp,
+                                                     dp]),
+                "rt_render_temporal_variance": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, C.POINTER(TemporalParams),
+                                                      C.POINTER(VarianceParams), C.c_uint32, vp, vp, C.POINTER(Stats)]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)

@@ -21,7 +21,7 @@ from typing import Optional, Sequence, Tuple, Union
 import numpy as np
 
 from ._lib import (RT_QUERY_ANY, RT_TEMPORAL_FIXED_SEED, RT_TEMPORAL_RESET, CameraUBO, DenoiseParams, Hit, RtError, Stats,
-                   TemporalParams, check, lib)
+                   TemporalParams, VarianceParams, check, lib)
 from .scene import BuiltCpuData, Camera
 
 REFERENCE_WIDTH = 1280          # VulkanEngine.java:45
@@ -304,6 +304,42 @@ class Renderer:
                                        d_out_rgba, d_out_radiance, stream, C.byref(t) if t is not None else None))
         return t.value if t is not None else None
 
+    def temporal_moments_device(self, width: int, height: int, camera, d_radiance: int, d_hits: int, d_hist_out: int,
+                                d_mom_out: int, prev_camera=None, d_hist_prev: Optional[int] = None,
+                                d_hits_prev: Optional[int] = None, d_mom_prev: Optional[int] = None,
+                                d_out_rgba: Optional[int] = None, d_out_radiance: Optional[int] = None,
+                                params: Optional[TemporalParams] = None, stream: Optional[int] = None,
+                                ms: bool = False):
+        """temporal_device with luminance moments (rt_temporal_moments_device,
+        DESIGN.md §4j): d_mom_out receives (m1, m2) per pixel, 8 bytes each;
+        d_mom_prev is the previous frame's, None exactly when the other
+        previous-frame inputs are.  The history and the display outputs are
+        temporal_device's bit for bit."""
+        t = C.c_double() if ms else None
+        check(lib().rt_temporal_moments_device(
+            self._ctx, width, height, C.byref(_ubo(camera)) if camera is not None else None, d_radiance, d_hits,
+            C.byref(_ubo(prev_camera)) if prev_camera is not None else None, d_hist_prev, d_hits_prev,
+            C.byref(params) if params is not None else None, d_hist_out, d_out_rgba, d_out_radiance, stream,
+            C.byref(t) if t is not None else None, d_mom_prev, d_mom_out))
+        return t.value if t is not None else None
+
+    def denoise_variance_device(self, width: int, height: int, d_hist: int, d_mom: int, d_hits: int, d_workspace: int,
+                                d_out_rgba: Optional[int] = None, d_out_radiance: Optional[int] = None,
+                                params: Optional[VarianceParams] = None, stream: Optional[int] = None,
+                                ms: bool = False):
+        """Enqueue the variance-guided filter of one whole frame between device
+        buffers (raw device pointers; rt_denoise_variance_device, DESIGN.md
+        §4j) on a HIP stream handle: d_hist and d_mom as
+        temporal_moments_device writes them (never written), the workspace is
+        denoise_workspace_bytes bytes.  Asynchronous unless ms, which waits and
+        returns the device time of the estimate and the passes in milliseconds."""
+        t = C.c_double() if ms else None
+        check(lib().rt_denoise_variance_device(self._ctx, width, height, d_hist, d_mom, d_hits,
+                                               C.byref(params) if params is not None else None, d_workspace,
+                                               d_out_rgba, d_out_radiance, stream,
+                                               C.byref(t) if t is not None else None))
+        return t.value if t is not None else None
+
     def temporal(self, radiance, hits, camera, prev_camera=None, hist_prev=None, hits_prev=None,
                  params: Optional[TemporalParams] = None):
         """The accumulation on host arrays: radiance float32 [H, W, 3] and
@@ -332,22 +368,31 @@ class Renderer:
     def render_temporal(self, camera, width: int, height: int, max_bounces: int = REFERENCE_MAX_BOUNCES,
                         params: Optional[TemporalParams] = None, denoise: Optional[DenoiseParams] = None,
                         reset: bool = False, fixed_seed: bool = False, radiance: bool = False, stats: bool = False,
-                        adaptive: bool = False):
+                        adaptive: bool = False, variance=None):
         """One frame of a temporally accumulated sequence (rt_render_temporal):
         render with a new sample per camera.frame_count (fixed_seed: the
         context's extensions as they are), first-hit buffer, reprojection of
         the context's history of the previous call, and with `denoise` the
         spatial filter after it.  adaptive: the history-adaptive filter runs on
         the new history record instead (rt_render_temporal_adaptive; `denoise`
-        None = its defaults); the two kinds of call share one history.  reset
-        drops the history first.  Returns
+        None = its defaults); the two kinds of call share one history.
+        variance (True = the defaults, or a VarianceParams): the
+        variance-guided filter on a history with luminance moments instead
+        (rt_render_temporal_variance; not with `denoise` or
+        adaptive); a call after one of the other kinds starts a new sequence.
+        reset drops the history first.  Returns
         (rgba, radiance or None, stats dict or None); ms = render + temporal
         (+ filter).  One device, no active spheres, extensions bit 4 off."""
         rgba = np.empty((height, width, 4), dtype=np.uint8)
         rad = np.empty((height, width, 3), dtype=np.float32) if radiance else None
         st = Stats() if stats else None
         flags = (RT_TEMPORAL_RESET if reset else 0) | (RT_TEMPORAL_FIXED_SEED if fixed_seed else 0)
-        call = lib().rt_render_temporal_adaptive if adaptive else lib().rt_render_temporal
+        if variance is not None and variance is not False:
+            if adaptive or denoise is not None:
+                raise ValueError("render_temporal: variance excludes adaptive and denoise")
+            call, denoise = lib().rt_render_temporal_variance, (None if variance is True else variance)
+        else:
+            call = lib().rt_render_temporal_adaptive if adaptive else lib().rt_render_temporal
         check(call(self._ctx, C.byref(_ubo(camera)), width, height, max_bounces,
                    C.byref(params) if params is not None else None,
                    C.byref(denoise) if denoise is not None else None, flags, rgba.ctypes.data,
@@ -412,7 +457,7 @@ class HipEngine:
                  height: int = REFERENCE_HEIGHT, max_bounces: int = REFERENCE_MAX_BOUNCES,
                  device_ids: Sequence[int] = (0,), collect_stats: bool = False, pipelined: bool = True,
                  inflight: int = 4, denoise: Optional[DenoiseParams] = None,
-                 temporal: Optional[TemporalParams] = None, adaptive: bool = False):
+                 temporal: Optional[TemporalParams] = None, adaptive: bool = False, variance=None):
         self.frame_queue = frame_queue
         # pipelined: `inflight` frames in flight (rt_render_async, one slot and
         # trace stream each), so the frames' traces overlap each other and
@@ -424,8 +469,11 @@ class HipEngine:
         # filter runs after the accumulation.
         # adaptive: the temporal path with the history-adaptive filter (render_temporal's adaptive=;
         # temporal None = the default parameters, denoise = the filter's parameters or None for its defaults).
+        # variance (True or a VarianceParams): the temporal path with the variance-guided filter
+        # (render_temporal's variance=; temporal None = the default parameters).
         self.denoise = denoise
-        self.temporal = TemporalParams() if adaptive and temporal is None else temporal
+        self.variance = None if variance is False else variance
+        self.temporal = TemporalParams() if (adaptive or self.variance is not None) and temporal is None else temporal
         self.adaptive = bool(adaptive)
         self.temporal_frames = 0
         self.pipelined = pipelined and not collect_stats and denoise is None and self.temporal is None
@@ -498,7 +546,7 @@ class HipEngine:
                         ubo.frame_count = self.temporal_frames
                         rgba, _, st = renderer.render_temporal(ubo, self.width, self.height, self.max_bounces,
                                                                self.temporal, self.denoise, stats=self.collect_stats,
-                                                               adaptive=self.adaptive)
+                                                               adaptive=self.adaptive, variance=self.variance)
                         self.temporal_frames += 1
                     elif self.denoise is not None:
                         rgba, _, st = renderer.render_denoised(ubo, self.width, self.height, self.max_bounces,

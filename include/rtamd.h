@@ -501,6 +501,83 @@ int rt_render_temporal_adaptive(rt_ctx* ctx, const rt_camera_ubo* cam, int width
                                 const rt_temporal_params* tparams, const rt_denoise_params* dparams, uint32_t flags,
                                 uint8_t* out_rgba, float* out_radiance, rt_stats* stats);
 
+/* ------------------------------------------------- variance-guided denoise -- */
+/* NON-REFERENCE: the a-trous filter whose luminance tolerance is the pixel's
+ * own estimated noise, fed by luminance moments kept beside the history
+ * (SVGF's moments).  n says how many samples a pixel holds; the moments say
+ * whether what is left is noise or detail.
+ *
+ * A moments buffer is width*height records of 2 floats (m1, m2): the
+ * accumulated mean of the samples' luminance l = (0.2126 r + 0.7152 g) +
+ * 0.0722 b of the linear colour, and of l * l.  8-byte aligned.
+ *
+ * rt_temporal_moments_device is rt_temporal_device with the moments: the same
+ * arguments, checks and kernel contract, and its history, radiance and RGBA8
+ * are rt_temporal_device's bit for bit.  d_mom_prev (the previous frame's
+ * moments) is NULL exactly when the other three previous-frame inputs are;
+ * d_mom_out is required.  A pixel without a hit, without history or without a
+ * taken tap gets (l, l * l) of its own sample; otherwise the moments are
+ * gathered with the colour's taps and weights and blended with its 1 / nn.
+ * Additional RT_ERR_INVALID_ARG: a moments buffer not 8-byte aligned, a
+ * partial previous set, d_mom_out overlapping any input or output.  Option
+ * "temporal_tile" applies. */
+int rt_temporal_moments_device(rt_ctx* ctx, int width, int height,
+                               const rt_camera_ubo* cam, const float* d_radiance, const rt_hit* d_hits,
+                               const rt_camera_ubo* prev_cam, const void* d_hist_prev, const rt_hit* d_hits_prev,
+                               const rt_temporal_params* params,
+                               void* d_hist_out, void* d_out_rgba, float* d_out_radiance, void* stream, double* ms,
+                               const void* d_mom_prev, void* d_mom_out);
+/* The filter.  An estimate gives every live pixel (tri >= 0 and n >= 1, as the
+ * adaptive filter's) the variance of its mean, v = max(0, m2 - m1^2) /
+ * max(n - 1, 1); where the history is shorter than min_history, the larger of
+ * that and a spatial estimate over the 7x7 window, weighted by the normal and
+ * plane terms of the guides.  Then rt_denoise_device's passes with three
+ * changes: the luminance term is y = the luminance difference / (sigma_lum *
+ * sqrt(v blurred 3x3) + 1e-6); v is filtered along with the colour (weights
+ * squared), so the tolerance tightens pass by pass; and a pixel with n samples
+ * is filtered in the first max(0, iterations - floor(log2 n)) passes only, as
+ * rt_denoise_history_device's.  With n >= 2^iterations everywhere the result
+ * is sqrt(c) whatever the moments hold.  The contract, operation by operation
+ * in IEEE binary32, is DESIGN.md §4j (tests/variance_ref.py restates it in
+ * numpy, bit for bit).  Added at ABI version 6 without a bump: no existing
+ * struct or argument list changed. */
+typedef struct rt_variance_params { int32_t iterations;        /* 1..6 */
+                                    int32_t normal_power_log2; /* 0..10 */
+                                    float sigma_depth, sigma_lum; /* finite, > 0 */
+                                    int32_t min_history;       /* 1..1024 */
+                                    int32_t reserved[3]; } rt_variance_params;   /* 32 B */
+/* The defaults: 4 passes, normal_power_log2 7, sigma_depth 0.005, sigma_lum 1.0,
+ * min_history 4 (reserved 0). */
+void rt_variance_default_params(rt_variance_params* out);
+/* One whole width x height frame on device 0 of ctx, between DEVICE buffers:
+ * d_hist (16-byte aligned), d_mom (8-byte aligned) and d_hits (16-byte
+ * aligned) in, none of them written; d_out_rgba and / or d_out_radiance out,
+ * as rt_denoise_device's; d_workspace: rt_denoise_workspace_bytes bytes,
+ * 16-byte aligned, left as scratch (two halves of records (c.r, c.g, c.b, v)).
+ * params NULL = the defaults.  Stream and ms as rt_denoise_device.  Allocates
+ * nothing and touches no render, query or temporal state ("plain_kernels"
+ * included).  The outputs must not overlap the inputs, the workspace or each
+ * other, nor the workspace an input.  RT_ERR_INVALID_ARG: a null input, both
+ * outputs null, a bad size or parameter, a misaligned buffer, an overlap.
+ * Options "denoise_kernel", "denoise_pass" and "variance_stage" apply. */
+int rt_denoise_variance_device(rt_ctx* ctx, int width, int height, const void* d_hist, const void* d_mom,
+                               const rt_hit* d_hits, const rt_variance_params* params, void* d_workspace,
+                               void* d_out_rgba, float* d_out_radiance, void* stream, double* ms);
+/* rt_render_temporal with the variance-guided filter: the frame is rendered and
+ * its hit records taken as rt_render_temporal does it,
+ * rt_temporal_moments_device blends it into the context's history and a
+ * context-owned ping-pong pair of moments buffers, then
+ * rt_denoise_variance_device filters the new history record into the outputs.
+ * vparams NULL = the defaults.  The history keeps the unfiltered accumulation.
+ * Same flags, same refusals and same history-drop rules as rt_render_temporal.
+ * rt_render_temporal and rt_render_temporal_adaptive write no moments: a call
+ * that follows one of them finds moments that are not those of the current
+ * history and drops the history as RT_TEMPORAL_RESET does.  stats (nullable):
+ * the render's counters, ms = the render's device time + the two stages'. */
+int rt_render_temporal_variance(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                                const rt_temporal_params* tparams, const rt_variance_params* vparams, uint32_t flags,
+                                uint8_t* out_rgba, float* out_radiance, rt_stats* stats);
+
 /* Schedule options (no effect on results, which are identical for every
  * setting):
  *   "kernel"        0 only: the one kernel, one lane per pixel (the
@@ -708,7 +785,15 @@ int rt_render_temporal_adaptive(rt_ctx* ctx, const rt_camera_ubo* cam, int width
  *                   consecutive pixels of a row, 2 = a wave on a 16x4 tile,
  *                   0 (default) = the one measured faster.
  *                   Same results; 1 and 2 are for tests and
- *                   tools/temporal_bench.py
+ *                   tools/temporal_bench.py.  Applies to
+ *                   rt_temporal_moments_device in the same way
+ *   "variance_stage" rt_denoise_variance_device: 0 = only the variance
+ *                   estimate is enqueued (tools/variance_bench.py times it
+ *                   this way; the outputs are not written); -1 (default) =
+ *                   the estimate and the passes.  "denoise_kernel" applies to
+ *                   its passes (2 = tiled at step 1, plain elsewhere; its own
+ *                   choice at 0); with "denoise_pass" i only
+ *                   pass i is enqueued, without the estimate
  *   "extensions"    NON-REFERENCE features, bits (default 0 = the reference's
  *                   shader exactly):
  *                   1 = honour sky_enabled (@68): a miss is black when it is 0
