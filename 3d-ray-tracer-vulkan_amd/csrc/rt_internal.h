@@ -231,17 +231,27 @@ struct LearnParams {
     int      rec_off;        // heavy-pixel waves ahead of the tile records (a fused launch in an order)
     int      learn_cost;     // 0 = lockstep steps + 2 x windows, 1 = wave duration
     int      order_split;    // percent (0 = every tile by cost)
-    double   bar_scale;      // heavy-pixel bar = bar_scale x total steps
+    // heavy-pixel bar = heavy_pixel_factor / 100.0 x ((total steps x concurrent) / resident), evaluated
+    // on the device in double in that order: learn_order's px_bar bit for bit
+    int      heavy_pixel_factor;   // percent
+    int      concurrent;     // launches of similar work in flight (>= 1)
+    int      resident;       // resident trace waves of the device (>= 1)
     int      cap;            // at most this many heavy pixels
     // option xcd_order (> 0, n a multiple of 8): tile_order position k runs on
     // XCD k % 8 (workgroups are dealt round-robin); XCD c gets the c-th eighth
     // of the tiles in the order of (row class, row, frame, column), a row's
-    // class being (row / xcd) % 8, still most expensive first within it
+    // class being (row / xcd) % 8, still most expensive first within it.
+    // Rows are the launch's own tile rows: on a band or list launch the rows
+    // of its bands packed one after another, not the frame's.  A launch whose
+    // tile count is no multiple of 8 keeps the plain order (learn_xcd_applies
+    // says which; rt_learn_copy reports it), and an order learned on the host
+    // is never grouped
     int      xcd = 0;
     int      tiles_x = 0, tiles_y = 0, frames = 0;
 };
 struct LearnScratch;         // device scratch (rt_learn.hip)
 size_t learn_scratch_bytes(int n);
+bool learn_xcd_applies(const LearnParams& lp);   // whether learn_on_device groups the order by XCD
 // Enqueues on stream s: writes d_order (n tile indices, most expensive first),
 // d_mask (n lane masks), d_hpix (<= cap heavy pixels, tile * 64 + lane, most
 // expensive first) and *d_nhpix (their count).  scratch: learn_scratch_bytes(n).

@@ -14,13 +14,19 @@
 //   learn_costs    tile k's cost (duration, or steps + 2 x windows), the
 //                  total lockstep steps and the costliest tile
 //   learn_split    option order_split: tiles below p% of the costliest keep
-//                  their raster order (cost key 0)
+//                  their raster order (cost key 0).  A tile's sort key is its
+//                  cost saturated at 2^32 - 1 and the costliest is saturated
+//                  the same way, so costs >= 2^32 (a wrapped duration is one)
+//                  tie at the top and pass every split
 //   radix sort     tiles by cost, descending and stable (rocPRIM), so equal
 //                  keys keep raster order, as the host's stable_sort did
 //   learn_cand     every pixel's key: its walk length and pixel index if the
-//                  length exceeds the heavy-pixel bar (the bulk estimate: total
-//                  steps x concurrent launches / resident waves x
-//                  heavy_pixel_factor), else 0
+//                  length exceeds the heavy-pixel bar, else 0.  The bar is the
+//                  host path's px_bar computed with its operations in its
+//                  order, in double: heavy_pixel_factor / 100.0 x ((total
+//                  steps x concurrent launches) / resident waves); a
+//                  pre-multiplied scale rounds differently around an integer
+//                  bar (resident waves = 6144 is no power of two)
 //   radix sort     the keys, descending (rocPRIM): length first, then the
 //                  lower pixel index, a total order, so the choice is the
 //                  host's whatever the candidate count
@@ -28,7 +34,9 @@
 //                  their tiles' lane masks
 //
 // The order only decides which wave traces a pixel and when, never what it
-// computes, so results are identical whatever these kernels choose.
+// computes, so results are identical whatever these kernels choose; what they
+// choose is checked word for word against tests/learn_ref.py
+// (tests/test_gpu_learn.py, through rt_learn_device and rt_learn_copy).
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "rt_internal.h"
@@ -108,7 +116,8 @@ __global__ __launch_bounds__(256) void learn_split(unsigned* __restrict__ key, i
                                                    int pct) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
-    const double split_at = (double)pct / 100.0 * (double)hdr->cmax;
+    const unsigned long long cmax = hdr->cmax;             // saturated as the keys are
+    const double split_at = (double)pct / 100.0 * (double)(cmax < 0xFFFFFFFFull ? cmax : 0xFFFFFFFFull);
     if (!((double)key[k] >= split_at)) key[k] = 0u;
 }
 
@@ -116,12 +125,13 @@ __global__ __launch_bounds__(256) void learn_split(unsigned* __restrict__ key, i
 // index, so a descending sort puts longer walks first and, among equal ones,
 // the lower pixel index first (the host's stable_sort order).
 __global__ __launch_bounds__(256) void learn_cand(const unsigned* __restrict__ lane, size_t nl,
-                                                  const LearnScratch* hdr, double bar_scale,
-                                                  unsigned long long* __restrict__ cand) {
+                                                  const LearnScratch* hdr, int factor, int concurrent,
+                                                  int resident, unsigned long long* __restrict__ cand) {
     const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nl) return;
     const unsigned len = lane[q];
-    const double bar = bar_scale * (double)hdr->total;
+    const double bulk = (double)hdr->total * (double)concurrent / (double)resident;
+    const double bar = factor / 100.0 * bulk;            // learn_order's px_bar, operation for operation
     cand[q] = (double)len > bar ? ((unsigned long long)len << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)q)
                                 : 0ull;
 }
@@ -179,6 +189,11 @@ __global__ __launch_bounds__(256) void xcd_place(const int* __restrict__ sorted,
 
 size_t learn_scratch_bytes(int n) { return layout(n).total; }
 
+bool learn_xcd_applies(const LearnParams& lp) {
+    return lp.xcd > 0 && lp.n % 8 == 0 && lp.tiles_x > 0 && lp.tiles_y > 0 && lp.frames > 0 &&
+           (long long)lp.tiles_x * lp.tiles_y * lp.frames == lp.n;
+}
+
 hipError_t learn_on_device(const LearnParams& lp, const unsigned long long* rec, const unsigned* lane,
                            void* scratch, int* d_order, unsigned long long* d_mask, int* d_hpix, int* d_nhpix,
                            hipStream_t s) {
@@ -203,8 +218,7 @@ hipError_t learn_on_device(const LearnParams& lp, const unsigned long long* rec,
     size_t tb = L.temp_bytes;
     e = rocprim::radix_sort_pairs_desc(base + L.temp, tb, key_in, key_out, val_in, d_order, lp.n, 0, 32, s);
     if (e != hipSuccess) return e;
-    if (lp.xcd > 0 && lp.n % 8 == 0 && lp.tiles_x > 0 && lp.tiles_y > 0 && lp.frames > 0 &&
-        (long long)lp.tiles_x * lp.tiles_y * lp.frames == lp.n) {
+    if (learn_xcd_applies(lp)) {
         int* sorted = reinterpret_cast<int*>(base + L.cand);            // free until learn_cand
         hipLaunchKernelGGL(xcd_keys, dim3(g), dim3(256), 0, s, d_order, lp.n, lp.tiles_x, lp.tiles_y, lp.frames,
                            lp.xcd, key_in, val_in);
@@ -218,7 +232,7 @@ hipError_t learn_on_device(const LearnParams& lp, const unsigned long long* rec,
     const size_t nl = (size_t)lp.n * 64;
     unsigned long long* cand_out = reinterpret_cast<unsigned long long*>(base + L.cand_out);
     hipLaunchKernelGGL(learn_cand, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, lane, nl, hdr,
-                       lp.bar_scale, cand);
+                       lp.heavy_pixel_factor, std::max(1, lp.concurrent), std::max(1, lp.resident), cand);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     tb = L.temp_bytes;
     e = rocprim::radix_sort_keys_desc(base + L.temp, tb, cand, cand_out, nl, 0, 64, s);

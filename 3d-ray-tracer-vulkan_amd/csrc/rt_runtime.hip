@@ -266,7 +266,12 @@ struct PerDevice {
                    int* d_hpix; int n_hpix; unsigned long long* d_mask;
                    bool pending = false;      // learned on the device, heavy-pixel count not read yet
                    void* d_base = nullptr;    // one allocation holding d_order, d_mask, d_hpix, d_nhpix
-                   int* d_nhpix = nullptr; };
+                   int* d_nhpix = nullptr;
+                   // rt_learn_copy: what the learning was given, whether the device kernels grouped
+                   // the order by XCD, and which learning launch it came from (learn_seq then)
+                   rt_learn_params given = {};
+                   bool xcd_applied = false;
+                   uint64_t seq = 0; };
     // device-side learning (rt_learn.hip): one at a time per device; its
     // scratch, the pinned heavy-pixel count it reports and the event after it
     void*        d_learn_scratch = nullptr;
@@ -277,6 +282,7 @@ struct PerDevice {
     bool         learn_oom = false;           // device learning's scratch did not fit: learn on the host
     bool         learning_device = false;     // the learning launch being planned learns on the device
     int          learning_rec_off = 0;        // its heavy-pixel waves ahead of the tile records
+    uint64_t     learn_seq = 0;               // learning launches planned so far: d_learn holds the newest's records
     // option heavy_tiles: auxiliary streams (round robin) for the concurrent heavy-tile launch
     hipStream_t  aux[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t   aux_fork[4] = {nullptr, nullptr, nullptr, nullptr}, aux_join[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -662,6 +668,7 @@ static int plan_order(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_ca
     p.learning_frames = a.n_frames;
     p.learning_device = device;
     p.learning_rec_off = 0;
+    ++p.learn_seq;
     // Option learn_alone: the learning launch waits for the device to drain,
     // so its wave durations (the order's cost) are not those of waves that
     // shared the GPU with other launches in flight at that moment.
@@ -723,12 +730,18 @@ static int learn_order_device(const rt_ctx* ctx, PerDevice& p, hipStream_t s) {
     lp.learn_cost = ctx->learn_cost;
     lp.order_split = ctx->order_split;
     // the host path's bar: heavy_pixel_factor% x (total steps x concurrent / resident waves)
-    lp.bar_scale = ctx->heavy_pixel_factor / 100.0 * (double)conc / (double)std::max(1, p.n_cu * kResidentPerCu);
+    lp.heavy_pixel_factor = ctx->heavy_pixel_factor;
+    lp.concurrent = conc;
+    lp.resident = std::max(1, p.n_cu * kResidentPerCu);
     lp.cap = cap;
     lp.xcd = ctx->xcd_order;
     lp.tiles_x = p.learning_tx;
     lp.tiles_y = p.learning_ty;
     lp.frames = p.learning_frames;
+    o.given = rt_learn_params{lp.rec_off, lp.learn_cost, lp.order_split, lp.heavy_pixel_factor, lp.concurrent,
+                              lp.resident, lp.cap, lp.xcd, lp.tiles_x, lp.tiles_y, lp.frames, 0};
+    o.xcd_applied = learn_xcd_applies(lp);
+    o.seq = p.learn_seq;
     hipError_t e = learn_on_device(lp, p.d_learn, p.d_learn_lane, p.d_learn_scratch, o.d_order, o.d_mask, o.d_hpix,
                                    o.d_nhpix, s);
     if (e == hipSuccess) e = hipMemcpyAsync(p.h_nhpix, o.d_nhpix, sizeof(int), hipMemcpyDeviceToHost, s);
@@ -762,7 +775,8 @@ static int learn_order(const rt_ctx* ctx, PerDevice& p, const TraceArgs& a, hipS
     for (size_t k = 0; k < n; ++k) {
         const unsigned long long* r = &rec[k * kDiagWords];
         steps[k] = r[4] + 2 * r[5];
-        cost[k] = learn_cost == 0 ? steps[k] : r[1] - r[0];
+        // saturated like the device path's 32-bit sort keys (rt_learn.hip): costs >= 2^32 tie
+        cost[k] = std::min<unsigned long long>(learn_cost == 0 ? steps[k] : r[1] - r[0], 0xFFFFFFFFull);
     }
     std::vector<int> order(n);
     for (size_t k = 0; k < n; ++k) order[k] = (int)k;
@@ -844,6 +858,10 @@ static int learn_order(const rt_ctx* ctx, PerDevice& p, const TraceArgs& a, hipS
         p.orders.erase(p.orders.begin());
     }
     PerDevice::Order o{p.learning_key, nullptr, n, heavy, nullptr, (int)hpix.size(), nullptr};
+    o.given = rt_learn_params{0, learn_cost, ctx->order_split, ctx->heavy_pixel_factor, std::max(1, concurrent),
+                              std::max(1, p.n_cu * kResidentPerCu), cap_waves, 0, p.learning_tx, p.learning_ty,
+                              p.learning_frames, 0};
+    o.seq = p.learn_seq;
     hipError_t e = hipMalloc(&o.d_order, n * sizeof(int));
     if (e == hipSuccess) e = hipMemcpy(o.d_order, order.data(), n * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc(&o.d_mask, n * sizeof(unsigned long long));
@@ -2968,6 +2986,79 @@ int rt_diag_copy(rt_ctx* ctx, void* dst, size_t cap_words, size_t* n_words) {
         RT_HIP_CHECK(hipDeviceSynchronize());
         RT_HIP_CHECK(hipMemcpy(dst, p.d_diag, std::min(cap_words, p.diag_used) * 8, hipMemcpyDeviceToHost));
     }
+    return RT_OK;
+}
+
+int rt_learn_device(rt_ctx* ctx, const void* d_records, const void* d_lanes, int n_tiles, const rt_learn_params* params,
+                    void* d_order, void* d_mask, void* d_hpix, void* d_count, void* stream) {
+    if (!ctx || !d_records || !d_lanes || !params || !d_order || !d_mask || !d_count) {
+        set_error("rt_learn_device: null argument");
+        return RT_ERR_INVALID_ARG;
+    }
+    const rt_learn_params& g = *params;
+    // 64 x n_tiles pixel keys are counted in an int
+    if (n_tiles < 1 || n_tiles > (1 << 24) || g.rec_off < 0 || g.rec_off > (1 << 24) || (g.learn_cost & ~1) ||
+        g.order_split < 0 || g.order_split > 100 || g.heavy_pixel_factor < 1 || g.concurrent < 1 || g.resident < 1 ||
+        g.cap < 0 || g.xcd < 0 || g.tiles_x < 0 || g.tiles_y < 0 || g.frames < 0 || (g.cap > 0 && !d_hpix)) {
+        set_error("rt_learn_device: bad tile count or parameters");
+        return RT_ERR_INVALID_ARG;
+    }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    LearnParams lp;
+    lp.n = n_tiles;
+    lp.rec_off = g.rec_off;
+    lp.learn_cost = g.learn_cost;
+    lp.order_split = g.order_split;
+    lp.heavy_pixel_factor = g.heavy_pixel_factor;
+    lp.concurrent = g.concurrent;
+    lp.resident = g.resident;
+    lp.cap = g.cap;
+    lp.xcd = g.xcd;
+    lp.tiles_x = g.tiles_x;
+    lp.tiles_y = g.tiles_y;
+    lp.frames = g.frames;
+    void* scratch = nullptr;
+    if (hipMalloc(&scratch, learn_scratch_bytes(n_tiles)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("rt_learn_device: out of device memory for the scratch");
+        return RT_ERR_OOM;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = learn_on_device(lp, static_cast<const unsigned long long*>(d_records),
+                                   static_cast<const unsigned*>(d_lanes), scratch, static_cast<int*>(d_order),
+                                   static_cast<unsigned long long*>(d_mask), static_cast<int*>(d_hpix),
+                                   static_cast<int*>(d_count), s);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    RT_HIP_CHECK(e);
+    RT_HIP_CHECK(e2);
+    return RT_OK;
+}
+
+int rt_learn_copy(rt_ctx* ctx, rt_learn_info* info, int32_t* order, uint64_t* mask, int32_t* hpix, uint64_t* records,
+                  uint32_t* lanes) {
+    if (!ctx || !info) { set_error("rt_learn_copy: null argument"); return RT_ERR_INVALID_ARG; }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    RT_HIP_CHECK(hipDeviceSynchronize());        // a learning in flight has finished: its count is in pinned memory
+    poll_learning(p);
+    if (p.orders.empty()) { set_error("rt_learn_copy: no order has been learned"); return RT_ERR_INVALID_ARG; }
+    const PerDevice::Order& o = p.orders.back();  // orders are appended as they are learned
+    const bool resident = o.seq == p.learn_seq && p.d_learn && p.d_learn_lane;
+    *info = rt_learn_info{(int32_t)o.n, o.n_hpix, o.heavy, o.d_base ? 1 : 0, o.xcd_applied ? 1 : 0, resident ? 1 : 0,
+                          o.given};
+    if ((records || lanes) && !resident) {
+        set_error("rt_learn_copy: a later learning launch has overwritten this order's records");
+        return RT_ERR_INVALID_ARG;
+    }
+    if (order) RT_HIP_CHECK(hipMemcpy(order, o.d_order, o.n * sizeof(int), hipMemcpyDeviceToHost));
+    if (mask) RT_HIP_CHECK(hipMemcpy(mask, o.d_mask, o.n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (hpix && o.n_hpix > 0) RT_HIP_CHECK(hipMemcpy(hpix, o.d_hpix, (size_t)o.n_hpix * sizeof(int), hipMemcpyDeviceToHost));
+    if (records)
+        RT_HIP_CHECK(hipMemcpy(records, p.d_learn + (size_t)o.given.rec_off * kDiagWords,
+                               o.n * kDiagWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (lanes) RT_HIP_CHECK(hipMemcpy(lanes, p.d_learn_lane, o.n * 64 * sizeof(unsigned), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

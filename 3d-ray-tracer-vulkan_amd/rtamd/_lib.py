@@ -44,6 +44,7 @@ EXPORTED = (
     "rt_denoise_history_device", "rt_render_temporal_adaptive",
     "rt_temporal_moments_device", "rt_variance_default_params", "rt_denoise_variance_device",
     "rt_render_temporal_variance",
+    "rt_learn_device", "rt_learn_copy",
 )
 
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
@@ -149,6 +150,16 @@ class VarianceParams(C.Structure):      # rt_variance_params; the defaults are r
         super().__init__(iterations, normal_power_log2, sigma_depth, sigma_lum, min_history)
 
 
+class LearnParams(C.Structure):         # rt_learn_params
+    _fields_ = [(k, C.c_int32) for k in ("rec_off", "learn_cost", "order_split", "heavy_pixel_factor", "concurrent",
+                                         "resident", "cap", "xcd", "tiles_x", "tiles_y", "frames", "reserved")]
+
+
+class LearnInfo(C.Structure):           # rt_learn_info
+    _fields_ = [(k, C.c_int32) for k in ("n_tiles", "n_hpix", "heavy", "on_device", "xcd_applied",
+                                         "records_resident")] + [("params", LearnParams)]
+
+
 RT_QUERY_ANY = 1
 RT_TEMPORAL_RESET = 1           # rt_render_temporal's flags
 RT_TEMPORAL_FIXED_SEED = 2
@@ -156,6 +167,7 @@ RT_TEMPORAL_FIXED_SEED = 2
 assert C.sizeof(CameraUBO) == 80
 assert C.sizeof(Ray) == 32 and C.sizeof(Hit) == 32 and C.sizeof(DenoiseParams) == 16
 assert C.sizeof(TemporalParams) == 16 and C.sizeof(VarianceParams) == 32
+assert C.sizeof(LearnParams) == 48 and C.sizeof(LearnInfo) == 72
 
 _lock = threading.Lock()
 _lib = None
@@ -252,6 +264,8 @@ def lib() -> C.CDLL:
                                                      dp]),
                 "rt_render_temporal_variance": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, C.POINTER(TemporalParams),
                                                       C.POINTER(VarianceParams), C.c_uint32, vp, vp, C.POINTER(Stats)]),
+                "rt_learn_device": (i32, [vp, vp, vp, i32, C.POINTER(LearnParams), vp, vp, vp, vp, vp]),
+                "rt_learn_copy": (i32, [vp, C.POINTER(LearnInfo), vp, vp, vp, vp, vp]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)

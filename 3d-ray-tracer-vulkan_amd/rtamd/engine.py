@@ -20,8 +20,8 @@ from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._lib import (RT_QUERY_ANY, RT_TEMPORAL_FIXED_SEED, RT_TEMPORAL_RESET, CameraUBO, DenoiseParams, Hit, RtError, Stats,
-                   TemporalParams, VarianceParams, check, lib)
+from ._lib import (RT_QUERY_ANY, RT_TEMPORAL_FIXED_SEED, RT_TEMPORAL_RESET, CameraUBO, DenoiseParams, Hit, LearnInfo,
+                   LearnParams, RtError, Stats, TemporalParams, VarianceParams, check, lib)
 from .scene import BuiltCpuData, Camera
 
 REFERENCE_WIDTH = 1280          # VulkanEngine.java:45
@@ -398,6 +398,37 @@ class Renderer:
                    C.byref(denoise) if denoise is not None else None, flags, rgba.ctypes.data,
                    rad.ctypes.data if rad is not None else None, C.byref(st) if st is not None else None))
         return rgba, rad, (st.as_dict() if st is not None else None)
+
+    # --- heavy-first learning diagnostics (include/rtamd.h rt_learn_device, rt_learn_copy) ---
+    def learn_device(self, d_records: int, d_lanes: int, n_tiles: int, d_order: int, d_mask: int, d_hpix: int,
+                     d_count: int, stream: Optional[int] = None, **params) -> None:
+        """The device learning on a caller's device buffers (raw pointers;
+        rt_learn_device): params are rt_learn_params's fields.  Waits for the
+        stream."""
+        lp = LearnParams(**params)
+        check(lib().rt_learn_device(self._ctx, d_records, d_lanes, n_tiles, C.byref(lp), d_order, d_mask, d_hpix,
+                                    d_count, stream))
+
+    def learn_copy(self, records: bool = True) -> dict:
+        """The newest learned order of device 0 (rt_learn_copy): a dict of
+        rt_learn_info's fields, with params flattened into it, and the arrays
+        order, mask, hpix and, with records while they are resident, the
+        learning launch's records [n, 8] and lanes [64 n].  Not for timing runs."""
+        info = LearnInfo()
+        check(lib().rt_learn_copy(self._ctx, C.byref(info), None, None, None, None, None))
+        n = info.n_tiles
+        out = {k: getattr(info, k) for k, _ in LearnInfo._fields_ if k != "params"}
+        out.update({k: getattr(info.params, k) for k, _ in LearnParams._fields_ if k != "reserved"})
+        order, mask = np.empty(n, np.int32), np.empty(n, np.uint64)
+        hpix = np.empty(info.n_hpix, np.int32)
+        rec = lanes = None
+        if records and info.records_resident:
+            rec, lanes = np.empty((n, 8), np.uint64), np.empty(64 * n, np.uint32)
+        check(lib().rt_learn_copy(self._ctx, C.byref(info), order.ctypes.data, mask.ctypes.data, hpix.ctypes.data,
+                                  rec.ctypes.data if rec is not None else None,
+                                  lanes.ctypes.data if lanes is not None else None))
+        out.update(order=order, mask=mask, hpix=hpix, records=rec, lanes=lanes)
+        return out
 
 
 class PinnedFrame:

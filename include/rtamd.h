@@ -748,7 +748,13 @@ int rt_render_temporal_variance(rt_ctx* ctx, const rt_camera_ubo* cam, int width
  *                   band to one eighth (r >= the tile rows: 8 contiguous
  *                   slabs), most expensive first within it, so each XCD's
  *                   L2 serves rays from fewer parts of the scene.  Same
- *                   results.
+ *                   results.  It needs a launch whose wave-tile count is a
+ *                   multiple of 8 (1080p: 32400 tiles, 1280x720: 14400);
+ *                   any other launch keeps the plain cost order.  The rows
+ *                   are the launch's own: a band or list launch groups the
+ *                   rows of its bands packed one after another, a batch
+ *                   the same rows of all its frames.  rt_learn_copy reports
+ *                   whether an order was grouped
  *   "order_split"   heavy_first: 0 = every tile in cost order; p in 1..100 =
  *                   only the tiles costing at least p percent of the
  *                   costliest go first (in cost order), the rest keep their
@@ -860,6 +866,53 @@ int rt_set_option(rt_ctx* ctx, const char* name, int64_t value);
  * (n_words = words recorded).  Not for timing runs. */
 int rt_diag_copy(rt_ctx* ctx, void* dst, size_t cap_words, size_t* n_words);
 int rt_get_option(rt_ctx* ctx, const char* name, int64_t* value);
+
+/* Diagnostics of the heavy-first learning (option "heavy_first"; DESIGN.md
+ * §4 item 4, csrc/rt_learn.hip): what a learning launch's records become.  Test and
+ * analysis entry points (tests/learn_ref.py is the model they are compared
+ * with); a host embedding the backend never needs them. */
+typedef struct rt_learn_params {
+    int32_t rec_off;            /* records ahead of tile 0's (heavy-pixel waves of a fused launch), >= 0 */
+    int32_t learn_cost;         /* 0 = words 4 + 2 x 5 of a record, 1 = word 1 - word 0 */
+    int32_t order_split;        /* 0..100 */
+    int32_t heavy_pixel_factor; /* percent, >= 1 */
+    int32_t concurrent;         /* launches in flight, >= 1 */
+    int32_t resident;           /* resident waves of the device, >= 1 */
+    int32_t cap;                /* at most this many heavy pixels, >= 0 */
+    int32_t xcd;                /* option xcd_order's r, 0 = off */
+    int32_t tiles_x, tiles_y, frames;   /* the launch's tile grid (xcd > 0) */
+    int32_t reserved;           /* 0 */
+} rt_learn_params;
+/* Runs the device learning on a caller's buffers, on device 0 of the context:
+ * d_records (params->rec_off + n_tiles records of 8 64-bit words, as
+ * rt_diag_copy describes them) and d_lanes (64 x n_tiles 32-bit walk lengths)
+ * in; d_order (n_tiles int32), d_mask (n_tiles 64-bit lane masks), d_hpix
+ * (min(cap, 64 x n_tiles) int32; the first *d_count are written) and d_count
+ * (one int32) out.  The kernels are the ones a learning launch is followed
+ * by, enqueued on `stream`; the call allocates their scratch, waits for the
+ * stream and frees it.  It reads no scene and touches no render state. */
+int rt_learn_device(rt_ctx* ctx, const void* d_records, const void* d_lanes, int n_tiles,
+                    const rt_learn_params* params, void* d_order, void* d_mask, void* d_hpix, void* d_count,
+                    void* stream);
+typedef struct rt_learn_info {
+    int32_t n_tiles;            /* tiles of the order */
+    int32_t n_hpix;             /* heavy pixels ("heavy_pixels_used" of a launch that runs in this order) */
+    int32_t heavy;              /* the host path's heavy-tile count (0 for a device-learned order) */
+    int32_t on_device;          /* 1 = learned by the device kernels, 0 = on the host */
+    int32_t xcd_applied;        /* 1 = the order is grouped by XCD (option xcd_order) */
+    int32_t records_resident;   /* 1 = the learning launch's records and lanes are still on the device */
+    rt_learn_params params;     /* what the learning was given (cap, resident waves, concurrency, tile grid ...) */
+} rt_learn_info;
+/* Copies the newest learned order of device 0 to the host, after waiting for
+ * the device and for a learning in flight: *info, order (n_tiles), mask
+ * (n_tiles), hpix (n_hpix), and the learning launch's own inputs, records
+ * (n_tiles records of 8 words, from the first tile's: past params.rec_off) and
+ * lanes (64 x n_tiles), which stay on the device until the next learning
+ * launch (records_resident; asked for when gone: RT_ERR_INVALID_ARG).  Every
+ * array is nullable: call once for *info, then with arrays of its sizes.
+ * RT_ERR_INVALID_ARG when nothing has been learned.  Not for timing runs. */
+int rt_learn_copy(rt_ctx* ctx, rt_learn_info* info, int32_t* order, uint64_t* mask, int32_t* hpix,
+                  uint64_t* records, uint32_t* lanes);
 
 /* Replaces VulkanEngine.cleanup. Null is accepted. */
 int rt_destroy(rt_ctx* ctx);

@@ -227,14 +227,16 @@ def test_stats_struct_order(renderer):
 def test_device_learning_matches_host_learning(renderer, cfg_k):
     """The order learned on the device (rt_learn.hip) picks the heavy pixels the
     host path picks from the same kind of learning launch (learn_cost 0: the
-    lockstep steps, a deterministic cost), and every frame stays the oracle's."""
+    lockstep steps, a deterministic cost): the same count, and through
+    rt_learn_copy the same heavy-pixel list, lane masks and tile order; every
+    frame stays the oracle's."""
     from rtamd import configs
     cfg = configs.get(cfg_k)
     built = cfg.build()
     W, H, B = cfg.width, cfg.height, cfg.max_bounces
     cam = configs.Camera((-25.0, 30.0, 141.5), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 20.0, W / H)
     ref = _oracle(built, cam.ubo_bytes(), W, H, B, row_step=9, radiance=False)[0]
-    used = {}
+    used, got = {}, {}
     try:
         renderer.set_option("learn_cost", 0)
         for dev in (1, 0):
@@ -244,10 +246,14 @@ def test_device_learning_matches_host_learning(renderer, cfg_k):
                 rgba = renderer.render(cam, W, H, B)[0]
                 assert np.array_equal(rgba[::9], ref), (dev, launch)
             used[dev] = renderer.get_option("heavy_pixels_used")
+            got[dev] = renderer.learn_copy(records=False)
+            assert got[dev]["on_device"] == dev and got[dev]["n_hpix"] == used[dev], dev
     finally:
         renderer.set_option("learn_cost", 1)
         renderer.set_option("learn_device", 1)
     assert used[1] > 0 and used[1] == used[0], used
+    for k in ("hpix", "mask", "order"):
+        assert np.array_equal(got[1][k], got[0][k]), k
 
 
 @pytest.mark.parametrize("align", [0, 1])
