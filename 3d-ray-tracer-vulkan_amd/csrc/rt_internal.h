@@ -124,6 +124,13 @@ constexpr int kExtNewSample = 16;   // seed += frame_count*W*H as kExtAccumulate
 
 constexpr int kMaxBatch = 16;  // frames per launch (rt_render_batch_device)
 
+// A split launch's queue header (TraceArgs::q_hdr): a 128-B line per queue.
+constexpr int kQHdrWords = 32;
+constexpr int kQCount = 0;     // entries claimed (failed claims included)
+constexpr int kQLimit = 1;     // ~(the lowest failed claim's base), 0 = no claim failed
+constexpr int kQTicket = 2;    // kernel-2 waves of the queue that have read the header
+constexpr int kMaxSplitQueues = 1024;   // option split_queues
+
 struct TraceArgs {
     DevScene scene;
     CamF     cams[kMaxBatch];   // frame f of the batch is seen through cams[f]
@@ -178,19 +185,24 @@ struct TraceArgs {
     int      list_stride;       // band_list per frame: frame f's at band_list + f * list_stride
                                 //   (0 = one list for every frame of the launch)
     const int* row_off = nullptr;   // per frame: its first output row (null: f * th); device memory
-    // Split launch (option split_bounce, accel walk): kernel 1
-    // packs each wave's paths still alive at bounce split_bounce into the
-    // wave's 64 ray slots (3 float4 each) and writes the wave's count; a scan
-    // makes q_prefix (q_waves + 1 entries); kernel 2 finishes the paths 64 per
-    // wave in slot order.  q_slots null: one kernel.
+    // Split launch (options split_bounce / split_pixels, accel walk; DESIGN.md
+    // §4b): a kernel-1 wave with n paths still alive at bounce split_bounce
+    // claims n entries (3 float4 each) of queue (its dispatch index mod
+    // q_queues) with one atomic add on the queue's count and writes them in
+    // lane order; a claim past q_cap leaves the paths with the wave and
+    // records its base in the queue's limit.  Kernel 2, one wave per pack of
+    // 64 entries, finishes the entries below min(count, limit, q_cap); the
+    // last of a queue's q_packs waves to draw its ticket zeroes the header.
+    // q_slots null: one kernel.
     int      split_bounce = 0;
-    float4*  q_slots = nullptr;
-    unsigned* q_count = nullptr;
-    unsigned* q_prefix = nullptr;
-    int      q_waves = 0;       // the slots' capacity in waves (launch_trace: kernel 1's waves)
-    int      q_grid = 0;        // kernel 2's one-wave workgroups
-    void*    q_temp = nullptr;  // the scan's temporary storage (rocPRIM), q_temp_bytes
-    size_t   q_temp_bytes = 0;
+    float4*  q_slots = nullptr;     // q_queues x q_cap entries
+    unsigned* q_hdr = nullptr;      // kQHdrWords per queue (kQCount, kQLimit, kQTicket), zero between launches
+    unsigned* q_overflow = nullptr; // waves whose claim did not fit (option split_overflow)
+    int      q_queues = 0;
+    int      q_cap = 0;             // entries per queue, a multiple of 64 (0: every claim fails)
+    unsigned long long q_pixels = 0;    // the launch's pixels: an entry's pixel index is below it
+    int      q_packs = 0;           // kernel 2's waves per queue: max(1, q_cap / 64)
+    int      q_spare = 0;
     // Query launch (launch_query; rtamd.h rt_query_rays_device, rt_render_hits_device):
     // lane i % 64 of wave i / 64 walks ray i of ray_in (2 float4 per rt_ray: origin.xyz, t_max;
     // dir.xyz, reserved), or with ray_in null the primary ray of its pixel, once, and writes its

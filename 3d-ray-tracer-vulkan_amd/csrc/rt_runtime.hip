@@ -4,7 +4,6 @@
 // barriers, staging image) has no counterpart: device buffers + one HIP
 // stream per device.
 #include "rt_internal.h"
-#include <rocprim/device/device_scan.hpp>
 
 #include "accel_build.h"
 
@@ -308,10 +307,14 @@ struct PerDevice {
     std::vector<BandList> band_lists;   // rt_render_batch_device's band lists on this device
     std::vector<Graph> graphs;
     unsigned     graph_next = 0;
-    // option split_bounce: one set of ray slots per launch stream (rt_internal.h
-    // TraceArgs::q_slots), grown to the largest launch seen on that stream
-    struct Slots { hipStream_t s; char* base; int waves; size_t temp_bytes; };
+    // split launches: one set of queues per launch stream (rt_internal.h
+    // TraceArgs::q_slots), grown to the largest launch seen on that stream:
+    // the headers of kMaxSplitQueues queues and the overflow word (zeroed
+    // when allocated; every split launch leaves the headers zero), then
+    // `bytes` of entries
+    struct Slots { hipStream_t s; char* base; size_t bytes; };
     std::vector<Slots> slots;
+    int          last_split = 0;    // the bounce the last launch split at (option "split_bounce_used", read only)
     // queries (rt_query_rays, rt_pick): the host forms' device staging, rays
     // then hits, grown to the largest batch; and L(0) of the reference's own
     // tree, which a query over an accel scene's reference records starts from
@@ -345,8 +348,15 @@ static constexpr int    kMaxHeavy = 256;
 // 28.5 GB per frame at the same frame time; config 3 (6.3 MB, L2-resident)
 // is 1.2% faster with 64 (profiles/r04/r4f).
 static constexpr size_t kWin32Bytes = 32ull << 20;
-// option split_bounce: the largest ray-slot allocation per launch stream
+// split launches: the largest queue allocation per launch stream
 static constexpr size_t kSplitSlotBytes = 256ull << 20;
+// option split_pixels' default: launches of 3 or more 1920x1080 frames, or of
+// one 3840x2160 frame, measured faster split (config 3 at 4 frames per launch
+// 0.1049-0.1063 against 0.1110-0.1119 ms per frame, at 3 frames 0.1090-0.1092
+// against 0.1116-0.1124); launches of 2 frames and of 1 measured slower
+// (0.1153-0.1157 against 0.1121-0.1125, 0.1344-0.1369 against 0.1174-0.1194;
+// profiles/split)
+static constexpr int kSplitPixelsDefault = 6000000;
 // The walk's buffer loads address the records with 32-bit byte offsets
 // (rt_trace.hip wbuf): at most 2^27 - 4 slots of 32 B (~45M triangles).
 static constexpr unsigned kMaxWalkSlots = (1u << 27) - 4;
@@ -446,6 +456,14 @@ struct rt_ctx {
     int  variance_stage = -1;      // rt_denoise_variance_device: 0 = enqueue the estimate alone (tools/variance_bench.py)
     int  split_bounce = 0;         // accel walk: paths alive at this bounce finish in a second kernel
                                    //   (0 = one kernel)
+    int  split_pixels = kSplitPixelsDefault;   // split_bounce 0: a plain format-0 accel launch of at least this
+                                   //   many pixels and 3 or more bounces splits at bounce 2 (0 = never)
+    int  split_queues = 256;       // split launch: queues the kernel-1 waves are dealt to (dispatch index mod):
+                                   //   8 measured 0.117-0.118 ms per frame on config 3, 64 0.1049-0.1063,
+                                   //   256 0.1045-0.1050, 1024 0.1044-0.1047 (profiles/split)
+    int  split_capacity = 64;      // split launch: the queues' entries together, per 1024 pixels of the
+                                   //   launch (survivors of bounce 2: 27 per 1024 on config 3; 0 = none:
+                                   //   every wave keeps its paths)
     // At the next upload: 0 = the reference's tree and order; 1 / 8 = the
     // binned-SAH tree in 1 / 8 (octant) layouts (accel_build.h).
     // Config 3 0.1279-0.1288 ms per frame against 0.2962-0.2964 for the
@@ -998,7 +1016,7 @@ static std::vector<uint64_t> launch_key(const TraceArgs& a, hipStream_t s) {
             (uint64_t)a.frame_count, P(a.accum), (uint64_t)a.walk, (uint64_t)a.block_waves, P(a.tile_order),
             (uint64_t)a.heavy_tiles, (uint64_t)(a.aux_stream != nullptr), (uint64_t)a.heavy_fused, P(a.heavy_px),
             (uint64_t)a.n_heavy_px, P(a.tile_mask), (uint64_t)a.coop_walk, (uint64_t)a.coop_win,
-            (uint64_t)a.split_bounce, P(a.q_slots), (uint64_t)a.q_waves, (uint64_t)a.q_grid};
+            (uint64_t)a.split_bounce, P(a.q_slots), (uint64_t)a.q_queues, (uint64_t)a.q_cap};
     for (int f = 0; f < a.n_frames; ++f) {
         const CamF& c = a.cams[f];
         for (float v : {c.ox, c.oy, c.oz, c.lx, c.ly, c.lz, c.hx, c.hy, c.hz, c.vx, c.vy, c.vz}) k.push_back(F(v));
@@ -1006,54 +1024,69 @@ static std::vector<uint64_t> launch_key(const TraceArgs& a, hipStream_t s) {
     return k;
 }
 
-// Option split_bounce (accel walk, no extensions or counters): the stream's
-// ray slots for a launch of tw x th x n_frames pixels.  Slots that must grow
-// wait for the launches already on their stream, which may still use them.
+// Split launches (options split_bounce / split_pixels): whether
+// this launch of tw x th x n_frames pixels splits, and the stream's queues for
+// it.  Queues that must grow wait for the launches already on their stream,
+// which may still use them.
 static int attach_slots(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, hipStream_t s) {
     a.q_slots = nullptr;
     a.split_bounce = 0;
-    if (!p.scene.n_layouts || ctx->split_bounce <= 0 || ctx->split_bounce >= a.max_bounces || a.ext || a.diag ||
-        a.counters)
+    a.q_queues = a.q_cap = a.q_packs = 0;
+    // what launch_trace splits: a plain launch over format-0 accel records
+    // without a cooperative tail (learning, counting, extension, half and
+    // wide launches stay one kernel)
+    if (!p.scene.n_layouts || p.scene.half || p.scene.wide || a.coop_lanes > 0 || a.ext || a.diag || a.counters)
         return RT_OK;
-    // kernel 1's waves, as launch_trace lays out its grid (an upper bound)
+    // the launch's pixels as launch_trace lays out its grid (an upper bound)
     const int tw_w = 8 << a.wave_tile, th_w = 8 >> a.wave_tile, bw = std::max(1, a.block_waves);
     const long long waves = (long long)((a.tw + bw * tw_w - 1) / (bw * tw_w)) * bw *
                             ((a.th + th_w - 1) / th_w) * (long long)a.n_frames;
-    // 3 KB of ray slots per wave (64 x 48 B): a one-frame 4K launch needs
-    // ~400 MB.  Past kSplitSlotBytes the launch stays one kernel (advisor,
-    // round 5: the slots only grow, per stream).
-    if (waves > (1 << 24) || (size_t)waves * 64 * 48 > kSplitSlotBytes) return RT_OK;
+    if (waves > (1 << 24)) return RT_OK;
+    const long long pixels = (long long)a.tw * a.th * a.n_frames;
+    // option split_bounce names the bounce; without it option split_pixels
+    // splits the launches that are large enough at bounce 2
+    int split = ctx->split_bounce;
+    if (split == 0 && ctx->split_pixels > 0 && a.max_bounces >= 3 && pixels >= ctx->split_pixels) split = 2;
+    if (split <= 0 || split >= a.max_bounces) return RT_OK;
+    // The queues hold split_capacity / 1024 of the launch's pixels, 48 B an
+    // entry, each queue a whole number of 64-entry packs: 25 MB at the default
+    // for 4 frames of 1920x1080 or one of 3840x2160.  Past kSplitSlotBytes
+    // the launch stays one kernel.
+    // (a small launch takes fewer queues, one per 64 waves: a queue's share
+    // of the survivors then stays near the launch's average)
+    const long long nq = std::max(1LL, std::min((long long)std::min(ctx->split_queues, kMaxSplitQueues), waves / 64));
+    const long long want = (waves * 64 * ctx->split_capacity + 1023) / 1024;
+    const long long cap = ctx->split_capacity > 0 ? ((want + nq - 1) / nq + 63) / 64 * 64 : 0;
+    const size_t bytes = (size_t)(nq * cap) * 48;
+    if (bytes > kSplitSlotBytes) return RT_OK;
+    const size_t hdr_bytes = (size_t)(kMaxSplitQueues + 1) * kQHdrWords * sizeof(unsigned);
     PerDevice::Slots* q = nullptr;
     for (auto& x : p.slots)
         if (x.s == s) { q = &x; break; }
-    if (!q || q->waves < waves) {
+    if (!q || q->bytes < bytes) {
         if (q) {
             RT_HIP_CHECK(hipStreamSynchronize(s));
             (void)hipFree(q->base);
             q->base = nullptr;
-            q->waves = 0;
+            q->bytes = 0;
         } else {
-            p.slots.push_back(PerDevice::Slots{s, nullptr, 0, 0});
+            p.slots.push_back(PerDevice::Slots{s, nullptr, 0});
             q = &p.slots.back();
         }
-        size_t tb = 0;
-        RT_HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, (const unsigned*)nullptr, (unsigned*)nullptr, 0u,
-                                             (size_t)waves, rocprim::plus<unsigned>()));
         void* base = nullptr;
-        const size_t bytes = (size_t)waves * 64 * 48 + 2 * ((size_t)waves * 4 + 256) + tb + 256;
-        RT_HIP_CHECK(hipMalloc(&base, bytes));
+        RT_HIP_CHECK(hipMalloc(&base, hdr_bytes + bytes + 256));
+        RT_HIP_CHECK(hipMemsetAsync(base, 0, hdr_bytes, s));
         q->base = static_cast<char*>(base);
-        q->waves = (int)waves;
-        q->temp_bytes = tb;
+        q->bytes = bytes;
     }
-    a.split_bounce = ctx->split_bounce;
-    a.q_slots = reinterpret_cast<float4*>(q->base);
-    a.q_count = reinterpret_cast<unsigned*>(q->base + (size_t)q->waves * 64 * 48);
-    a.q_prefix = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(a.q_count) + (size_t)q->waves * 4 + 256);
-    a.q_temp = reinterpret_cast<char*>(a.q_prefix) + (size_t)q->waves * 4 + 256;
-    a.q_temp_bytes = q->temp_bytes;
-    a.q_waves = q->waves;
-    a.q_grid = std::max(1, p.n_cu * 32);        // kernel 2: a full device of one-wave workgroups
+    a.split_bounce = split;
+    a.q_hdr = reinterpret_cast<unsigned*>(q->base);
+    a.q_overflow = a.q_hdr + (size_t)kMaxSplitQueues * kQHdrWords;
+    a.q_slots = reinterpret_cast<float4*>(q->base + hdr_bytes);
+    a.q_queues = (int)nq;
+    a.q_cap = (int)cap;
+    a.q_packs = (int)std::max(1LL, cap / 64);
+    a.q_pixels = (unsigned long long)pixels;
     return RT_OK;
 }
 
@@ -1066,9 +1099,11 @@ static int launch(const rt_ctx* ctx, PerDevice& p, const TraceArgs& a_in, hipStr
     // stream: a graph launch adds ~9 us between frames (profiles/r02/graph).
     const bool plain = !a.counters && !a.diag;          // the production build (option "plain_kernels")
     int nk = 1;
+    p.last_split = 0;                                   // (a launch with an auxiliary stream never splits)
     if (!ctx->graph || s == nullptr || a.counters || a.diag || !a.aux_stream) {
         RT_HIP_CHECK(launch_trace(a, s, &nk));
         if (plain) p.plain_kernels += (uint64_t)nk;
+        if (nk == 2 && a.q_slots) p.last_split = a.split_bounce;
         return RT_OK;
     }
     std::vector<uint64_t> key = launch_key(a, s);
@@ -2909,6 +2944,9 @@ static const Option kOptions[] = {
     one_of("accel_half", &rt_ctx::accel_half, 0, 1),
     one_of("accel_wide", &rt_ctx::accel_wide, 0, 1),
     in_range("split_bounce", &rt_ctx::split_bounce, 0, 64),
+    in_range("split_pixels", &rt_ctx::split_pixels, 0, 1 << 30),
+    in_range("split_queues", &rt_ctx::split_queues, 1, kMaxSplitQueues),
+    in_range("split_capacity", &rt_ctx::split_capacity, 0, 1024),
     in_range("heavy_stream", &rt_ctx::heavy_stream, 0, 2),
     one_of("graph", &rt_ctx::graph, 0, 1),
     one_of("diag", &rt_ctx::diag, 0, 1),
@@ -2968,6 +3006,24 @@ int rt_get_option(rt_ctx* ctx, const char* name, int64_t* value) {
     else if (is("heavy_tiles_used")) *value = p ? p->last_heavy : 0;
     else if (is("solo_lanes_used")) *value = p ? p->last_solo : 0;
     else if (is("plain_kernels")) *value = p ? (int64_t)p->plain_kernels : 0;
+    else if (is("split_bounce_used")) *value = p ? p->last_split : 0;
+    else if (is("split_overflow")) {
+        // diagnostic: waits for every device, then reads and zeroes each
+        // launch stream's count of kernel-1 waves whose claim did not fit
+        *value = 0;
+        for (PerDevice& d : ctx->dev) {
+            if (d.slots.empty()) continue;
+            RT_HIP_CHECK(hipSetDevice(d.device));
+            RT_HIP_CHECK(hipDeviceSynchronize());
+            for (auto& q : d.slots) {
+                unsigned* w = reinterpret_cast<unsigned*>(q.base) + (size_t)kMaxSplitQueues * kQHdrWords;
+                unsigned n = 0;
+                RT_HIP_CHECK(hipMemcpy(&n, w, sizeof n, hipMemcpyDeviceToHost));
+                RT_HIP_CHECK(hipMemset(w, 0, sizeof n));
+                *value += n;
+            }
+        }
+    }
     else if (is("hw_queues")) *value = ctx->hw_queues;
     // 1 when rt_render_async's slots cannot each have a hardware queue of their
     // own (async_slots + 2 > hw_queues: the slots' traces then share queues and

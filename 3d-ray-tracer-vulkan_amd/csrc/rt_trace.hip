@@ -39,8 +39,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "rt_internal.h"
 
 namespace rtamd {
@@ -883,9 +881,9 @@ constexpr int kFeatWin32 = 128;   // cooperative windows of 32 slots (option coo
 constexpr int kFeatPad = 256;     // the production kernels (cooperative tail, no extensions) on records
                                   //   with pad slots (leaf_align); every other variant always reads pad bits
 constexpr int kFeatQ1 = 4096;     // split launch, kernel 1: paths alive at bounce split_bounce go to the
-                                  //   launch's ray slots (compacted per wave, no atomics)
-constexpr int kFeatQ2 = 8192;     // split launch, kernel 2: the slotted paths from bounce split_bounce,
-                                  //   64 per wave in slot order
+                                  //   launch's queues (one claim per wave; a wave keeps what does not fit)
+constexpr int kFeatQ2 = 8192;     // split launch, kernel 2: the queued paths from bounce split_bounce,
+                                  //   64 per wave in queue order
 constexpr int kFeatHalf = 2048;   // option accel_half (with kFeatAccel): 16-B slots, half-precision internal
                                   //   boxes (accel_build.h format 1)
 constexpr int kFeatWide = 1024;   // option accel_wide (with kFeatAccel): the 4-wide tree (accel_build.h format 2),
@@ -1084,11 +1082,35 @@ void trace_simple(TraceArgs a) {
     // frontier_walk's per-wave frontiers (kFCap entries per wave; dynamic LDS,
     // sized by the launch for variants with kFeatFrontier or kFeatFused)
     extern __shared__ uint4 fr[];
-    // Split kernel 2: a fixed grid of one-wave workgroups; wave k takes the
-    // slotted paths 64k .. 64k + 63 (then 64 (k + grid) ..), in slot order.
-    unsigned q_k = Q2 ? blockIdx.x : 0u;
-    const unsigned q_total = Q2 ? a.q_prefix[a.q_waves - 1] + a.q_count[a.q_waves - 1] : 0u;
-    if (Q2 && q_k * 64u >= q_total) return;
+    // Split kernel 2: one-wave workgroups; wave g takes pack g / q_queues of
+    // queue g % q_queues: the queue's entries 64 pack .. 64 pack + 63 that
+    // kernel 1 wrote, which are those below its count, below the lowest
+    // failed claim's base (kept as its complement, so a reset header is all
+    // zero) and below the capacity.
+    unsigned q_first = 0u, q_valid = 0u;                 // this wave's first entry, the queue's written entries
+    if (Q2) {
+        const unsigned q = blockIdx.x % (unsigned)a.q_queues;
+        unsigned* const h = a.q_hdr + kQHdrWords * (size_t)q;
+        const unsigned cnt = __hip_atomic_load(h + kQCount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned lim = ~__hip_atomic_load(h + kQLimit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // both loads have returned before this wave draws its ticket: the
+        // queue's last wave to draw one zeroes the header for the stream's
+        // next launch, and by then every wave of the queue has read it
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) {
+            const unsigned t = __hip_atomic_fetch_add(h + kQTicket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (t + 1u == (unsigned)a.q_packs) {
+                __hip_atomic_store(h + kQCount, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(h + kQLimit, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(h + kQTicket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        q_valid = min(min(cnt, lim), (unsigned)a.q_cap);
+        q_first = (blockIdx.x / (unsigned)a.q_queues) * 64u;
+        if (q_first >= q_valid) return;
+        q_first += q * (unsigned)a.q_cap;                // (q_queues x q_cap entries fit 32 bits: attach_slots)
+        q_valid += q * (unsigned)a.q_cap;
+    }
     // One wave = one tile of 64 pixels, (8 << s) x (8 >> s) with s = a.wave_tile
     // (s = 0: 8x8, the reference's local_size 8x8x1, compute_dynamic_ray.comp:157);
     // a workgroup = block_waves (4 or 1) such tiles side by side.
@@ -1175,9 +1197,6 @@ void trace_simple(TraceArgs a) {
     // (a per-frame band list's -1 entries are padding rows: no pixel)
     const bool pixel = !Q2 && lx < a.tw && ly < a.th && (sub < 0 || lane == 0) && !((skip_lanes >> lane) & 1ull) &&
                        (a.list_stride == 0 || a.band_list[fr_i * a.list_stride + ly / a.band_h] >= 0);
-    // Split kernel 1: this wave's slot count starts at 0 (a wave whose paths
-    // all end before split_bounce never writes it again)
-    if (Q1 && lane == 0) a.q_count[k_wave] = 0u;
     const int coop_lanes = sub >= 0 ? 64 : a.coop_lanes;
     const float4* __restrict__ nodes = a.scene.nodes;
     const float4* __restrict__ leafs = a.scene.leafs;
@@ -1188,7 +1207,6 @@ void trace_simple(TraceArgs a) {
     unsigned long long d_iters = 0, d_windows = 0, d_coop_t = 0;   // diag builds only
     unsigned long long d_lane_windows = 0;           // diag: cooperative windows spent on this lane's walks
 
-  do {   // split kernel 2 loops over its packs of 64 slotted paths; every other kernel runs once
     uint32_t seed = 0;
     V3 o = {0.f, 0.f, 0.f}, d = {0.f, 0.f, 1.f};
     V3 att = {1.0f, 1.0f, 1.0f};
@@ -1197,26 +1215,23 @@ void trace_simple(TraceArgs a) {
     float tmax = kTMax;               // query: the ray's t_max, where its closest_t starts
     bool refq = false;                // query: a non-unit direction, walked in the reference's order
     if (Q2) {
-        // path i of the slot order: source wave w with prefix[w] <= i < prefix[w + 1]
-        const unsigned i = q_k * 64u + (unsigned)lane;
-        alive = i < q_total;
+        // entry i of the queue, one per lane
+        const unsigned i = q_first + (unsigned)lane;
+        alive = i < q_valid;
         b0 = a.split_bounce;
         if (alive) {
-            int lo = 0, hi = a.q_waves;                  // prefix[lo] <= i < prefix[hi] (prefix[q_waves] = total)
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (a.q_prefix[mid] <= i) lo = mid;
-                else hi = mid;
-            }
-            const float4* r = a.q_slots + 3 * ((size_t)lo * 64 + (i - a.q_prefix[lo]));
+            const float4* r = a.q_slots + 3 * (size_t)i;
             const float4 r0 = r[0], r1 = r[1], r2 = r[2];
             o = {r0.x, r0.y, r0.z};
             d = {r0.w, r1.x, r1.y};
             att = {r1.z, r1.w, r2.x};
             seed = __float_as_uint(r2.y);
-            const int pq = __float_as_int(r2.z);
-            lyo = pq / a.tw;
-            lx = pq - lyo * a.tw;
+            const unsigned pq = __float_as_uint(r2.z);
+            // (an entry kernel 1 wrote names a pixel of the launch; nothing
+            // else is ever stored through)
+            alive = pq < a.q_pixels;
+            lyo = (int)(pq / (unsigned)a.tw);
+            lx = (int)(pq - (unsigned)lyo * (unsigned)a.tw);
         }
     }
     if (QRY && a.ray_in) {
@@ -1253,18 +1268,34 @@ void trace_simple(TraceArgs a) {
     for (int b = b0; b < (QRY ? 1 : a.max_bounces); ++b) {   // (a query walks its ray once)
         if (__ballot(alive) == 0) break;
         if (Q1 && b == a.split_bounce) {
-            // Split kernel 1: the paths still alive leave for this wave's 64
-            // ray slots, packed in lane order (no atomics); kernel 2 takes them.
+            // Split kernel 1: the n paths still alive (n > 0 here) leave for
+            // n entries of this wave's queue, claimed with one atomic add and
+            // written in lane order; kernel 2 takes them.  A claim that does
+            // not fit leaves the paths with this wave, which walks on, and
+            // marks its base: claims only grow, so the entries below the
+            // lowest such base are exactly the written ones.
             const uint64_t m = __ballot(alive);
-            if (alive) {
-                float4* r = a.q_slots + 3 * ((size_t)k_wave * 64 + (size_t)lanes_below(m));
-                r[0] = make_float4(o.x, o.y, o.z, d.x);
-                r[1] = make_float4(d.y, d.z, att.x, att.y);
-                r[2] = make_float4(att.z, __uint_as_float(seed), __int_as_float(lyo * a.tw + lx), 0.0f);
+            const unsigned n = (unsigned)__popcll(m);
+            const unsigned q = (unsigned)k_wave % (unsigned)a.q_queues;
+            unsigned* const h = a.q_hdr + kQHdrWords * (size_t)q;
+            int base = 0;
+            if (lane == 0)
+                base = (int)__hip_atomic_fetch_add(h + kQCount, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            base = lane_i(base, 0);
+            if ((unsigned long long)(unsigned)base + n <= (unsigned long long)(unsigned)a.q_cap) {
+                if (alive) {
+                    float4* r = a.q_slots + 3 * ((size_t)q * (size_t)a.q_cap + (unsigned)base + (size_t)lanes_below(m));
+                    r[0] = make_float4(o.x, o.y, o.z, d.x);
+                    r[1] = make_float4(d.y, d.z, att.x, att.y);
+                    r[2] = make_float4(att.z, __uint_as_float(seed), __int_as_float(lyo * a.tw + lx), 0.0f);
+                }
+                alive = false;
+                break;
             }
-            if (lane == 0) a.q_count[k_wave] = (unsigned)__popcll(m);
-            alive = false;
-            break;
+            if (lane == 0) {
+                __hip_atomic_fetch_max(h + kQLimit, ~(unsigned)base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(a.q_overflow, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
         float closest = QRY ? tmax : kTMax;
         int hit = -1;
@@ -1623,8 +1654,6 @@ void trace_simple(TraceArgs a) {
     }
     // A path still alive here ran no bounce at all (max_bounces 0): black.
     if (!QRY && alive) finish_pixel<FEAT>(a, lx, lyo, V3{0.0f, 0.0f, 0.0f});
-    q_k += gridDim.x;
-  } while (Q2 && q_k * 64u < q_total);
     if (COUNT) flush_counters(a.counters, c_seg, c_node, c_tri, c_mat);
     if (DIAG) {
         diag_stamp(drec, 1);
@@ -1757,30 +1786,26 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels) {
         // or pixels out of an accel launch, and there is no frontier tail)
         if (a.q_slots && a.split_bounce > 0 && a.split_bounce < a.max_bounces && feat == 0 && !a.scene.half &&
             !a.scene.wide &&
-            !a.diag && !a.counters && (int)(grid.x * grid.y) * bw <= a.q_waves) {
+            !a.diag && !a.counters && a.q_queues > 0 && a.q_packs > 0) {
             // split launch: kernel 1 to bounce split_bounce,
-            // the scan of its per-wave counts, kernel 2 for the rest
-            ao.q_waves = (int)(grid.x * grid.y) * bw;
+            // kernel 2 for the queued paths, both on the launch's stream
             if (a.solo_lanes > 0)
                 hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ1 | kFeatSolo, 2>), grid, block, 0,
                                    stream, ao);
             else
                 hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ1, 2>), grid, block, 0, stream, ao);
-            size_t tb = a.q_temp_bytes;
-            const hipError_t se = rocprim::exclusive_scan(a.q_temp, tb, a.q_count, a.q_prefix, 0u,
-                                                          (size_t)ao.q_waves, rocprim::plus<unsigned>(), stream);
-            if (se != hipSuccess) return se;
             TraceArgs a2 = ao;
             a2.tile_order = nullptr;
             a2.split_n = 0;
             a2.block_waves = 1;
+            const dim3 grid2((unsigned)a.q_queues * (unsigned)a.q_packs);
             if (a.solo_lanes > 0)
-                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ2 | kFeatSolo, 2>), dim3(a.q_grid),
+                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ2 | kFeatSolo, 2>), grid2,
                                    dim3(64), 0, stream, a2);
             else
-                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ2, 2>), dim3(a.q_grid), dim3(64), 0,
+                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ2, 2>), grid2, dim3(64), 0,
                                    stream, a2);
-            if (kernels) *kernels = 2;                          // the frame kernels (q_scan aside)
+            if (kernels) *kernels = 2;
             return hipGetLastError();
         }
         if (a.scene.wide) {

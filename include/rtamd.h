@@ -620,16 +620,37 @@ int rt_render_temporal_variance(rt_ctx* ctx, const rt_camera_ubo* cam, int width
  *                   of accel launches (heavy_first still orders the tiles)
  *   "split_bounce"  accel walk, no extensions: b in 1..max_bounces-1 = a
  *                   frame's paths still alive at bounce b leave its kernel for
- *                   the wave's ray slots (packed per wave, no atomics), a scan
- *                   orders them and a second kernel finishes them 64 per wave,
- *                   so the few long late-bounce paths of a tile no longer hold
- *                   a whole wave; 0 (default) = one kernel.
- *                   Same frames; counting and diagnostic launches stay one
- *                   kernel.  Memory: 3 KB of ray slots per wave of a launch
- *                   (64 x 48 B), per launch stream, kept until rt_destroy; a
- *                   launch that would need more than 256 MB (e.g. a batch of
- *                   4K frames) stays one kernel.  Growing a stream's slots
- *                   synchronises that stream
+ *                   the launch's queues (a wave claims its paths' entries
+ *                   with one atomic add) and a second kernel on the same
+ *                   stream finishes them 64 per wave, so the few long
+ *                   late-bounce paths of a tile no longer hold a whole wave
+ *                   (DESIGN.md §4b); 0 (default) = "split_pixels" decides.
+ *                   Same frames: a wave whose claim does not fit finishes its
+ *                   own paths.  Format-0 accel records only; counting,
+ *                   learning, extension and cooperative-tail launches stay one
+ *                   kernel.  Memory per launch stream, kept until rt_destroy:
+ *                   "split_capacity" / 1024 of the largest launch's pixels x
+ *                   48 B (25 MB for 4 frames of 1920x1080); a launch that
+ *                   would need more than 256 MB stays one kernel.  Growing a
+ *                   stream's queues synchronises that stream
+ *   "split_pixels"  with "split_bounce" 0: a launch of at least this many
+ *                   pixels (all its frames together) and max_bounces >= 3
+ *                   splits at bounce 2; 0 = never.  0..2^30, default 6000000:
+ *                   3 or more 1920x1080 frames per launch, or one 3840x2160
+ *                   frame, measured faster split, 2 frames and 1 slower
+ *                   
+ *   "split_queues"  split launches: the number of queues; kernel-1 wave k
+ *                   appends to queue k mod this (a launch of fewer than 64
+ *                   waves per queue takes fewer).  1..1024, default 256
+ *   "split_capacity" split launches: the entries of all queues together, per
+ *                   1024 pixels of the launch (each queue a whole number of
+ *                   64-entry packs); 0 = no entries, every wave keeps its
+ *                   paths.  0..1024, default 64
+ *   "split_bounce_used" (rt_get_option only) the bounce device 0's last
+ *                   launch split at, 0 when it ran as one kernel
+ *   "split_overflow" (rt_get_option only; diagnostic, waits for the devices)
+ *                   kernel-1 waves whose claim did not fit their queue since
+ *                   the last read
  *   "accel_half"    at the next rt_upload_scene, accel records with the
  *                   internal nodes' boxes in IEEE half precision rounded
  *                   outward (16-B internal records instead of 32; leaves keep
