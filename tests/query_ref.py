@@ -69,11 +69,12 @@ def primary_rays(camera_ubo: bytes, width: int, height: int, tile=None) -> np.nd
     return make_rays(np.broadcast_to(org, (xs.size, 3)), np.stack([d[0] / ln, d[1] / ln, d[2] / ln], 1))
 
 
-def closest_hits(vertices, nodes, rays):
+def closest_hits(vertices, nodes, rays, on_node=None):
     """Returns (hits HIT_DTYPE[n], node_visits int64[n], tri_tests int64[n]).
     A ray with a non-finite origin / direction component or an all-zero
     direction is not walked (tri = -2, t = 0, no counts); t_max >= T_MAX or
-    NaN is T_MAX; a miss has tri = -1 and t = the effective t_max."""
+    NaN is T_MAX; a miss has tri = -1 and t = the effective t_max.
+    on_node(ray indices, the six slab products) sees every node visit."""
     V = np.frombuffer(bytes(vertices), np.float32)
     V = V[: (V.size // 12) * 12].reshape(-1, 3, 4)[:, :, :3]
     nb = np.frombuffer(bytes(nodes), np.uint8)
@@ -121,6 +122,8 @@ def closest_hits(vertices, nodes, rays):
             t0x = (BMIN[node, 0] - rox[w]) * ix; t1x = (BMAX[node, 0] - rox[w]) * ix
             t0y = (BMIN[node, 1] - roy[w]) * iy; t1y = (BMAX[node, 1] - roy[w]) * iy
             t0z = (BMIN[node, 2] - roz[w]) * iz; t1z = (BMAX[node, 2] - roz[w]) * iz
+        if on_node is not None:
+            on_node(act[w], (t0x, t1x, t0y, t1y, t0z, t1z))
         te = np.fmax(np.fmax(np.fmin(t0x, t1x), np.fmin(t0y, t1y)), np.fmin(t0z, t1z))
         tx = np.fmin(np.fmin(np.fmax(t0x, t1x), np.fmax(t0y, t1y)), np.fmax(t0z, t1z))
         hb = (tx > te) & (tx > T_MIN) & (te < closest[w])

@@ -3,11 +3,15 @@ include/rtamd.h "queries"), bit for bit against
 tests/query_ref.py (the reference's closest hit in numpy, pinned to the CPU
 oracle by tests/test_query_ref.py).
 
-Ray sources are rays whose walks the render suite already proves exact:
-primary rays and the per-bounce rays oracle/shader_np.py hands out (their
-origins lie on surfaces, so T_MIN matters), over random soups, the tie scenes
-and the adversarial scenes of the accel model's tests.  Every test runs on the
-accel tree in 8 layouts and in 1, and on the reference's own tree (accel 0).
+Ray sources here are the rays of jittered perspective cameras: primary rays
+and the per-bounce rays oracle/shader_np.py hands out (their origins lie on
+surfaces, so T_MIN matters), over random soups, the tie scenes and the
+adversarial scenes of the accel model's tests.  Such rays almost never have a
+zero, negative-zero or denormal component, an origin in a box plane, a hit
+exactly on an edge or a t_max equal to a hit's t: those are the rays of
+tests/designed_rays.py, queried in tests/test_gpu_designed_rays.py.  Every
+test runs on the accel tree in 8 layouts and in 1, and on the reference's own
+tree (accel 0).
 """
 import functools
 import os

@@ -28,17 +28,23 @@ def _scene(k, w, h):
 @pytest.mark.parametrize("name,k,w,h", _cases())
 def test_query_ref_is_the_oracle(name, k, w, h):
     built, cam = _scene(k, w, h)
-    rays = Q.primary_rays(cam.ubo_bytes(), w, h)
+    assert_is_the_oracle(name, built, cam.ubo_bytes(), w, h, mixed=k != 1)
+
+
+def assert_is_the_oracle(name, built, ubo, w, h, mixed=True):
+    """query_ref on the primary rays of the camera `ubo` against a 1-bounce
+    oracle frame; mixed: the frame must hold both hits and sky."""
+    rays = Q.primary_rays(ubo, w, h)
     hits, nv, nt = Q.closest_hits(built.model_vertex_data, built.flat_bvh_data, rays)
     _, rad, cnt = oracle_lib.render(built.model_vertex_data, built.model_material_data, built.flat_bvh_data,
-                                    cam.ubo_bytes(), w, h, 1)
+                                    ubo, w, h, 1)
     # a 1-bounce hit is always black (:229-231) and the sky never is (:81-85)
     black = (rad.reshape(-1, 3) == 0).all(1)
     assert np.array_equal(hits["tri"] >= 0, black), name
     assert (hits["tri"] >= -1).all()
     assert cnt["segments"] == len(rays)
     assert int(nv.sum()) == cnt["node_visits"] and int(nt.sum()) == cnt["tri_tests"], name
-    if k != 1:
+    if mixed:
         assert black.any() and not black.all(), name
     # every hit: the contract's hit_triangle on (ray, tri) gives the same t and normal bits
     idx, ok, t, nrm = Q.oracle_triangle_hits(built.model_vertex_data, rays, hits, np.full(len(rays), Q.T_MAX))
