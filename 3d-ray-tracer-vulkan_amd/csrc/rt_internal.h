@@ -211,6 +211,14 @@ struct TraceArgs {
     const float4* ray_in = nullptr;
     float4*  hit_out = nullptr;
     int      any_hit = 0;       // RT_QUERY_ANY: a lane's walk stops at its first consistent hit
+    // Samples launch (rtamd.h rt_render_samples_device): a batch launch whose frames are
+    // consecutive samples of one camera.  Both fields are read by the extension builds only (kFeatExt code),
+    // and follow every field the other kernels read.
+    int      sample_step = 0;   // frame f of the launch seeds with frame_count + f * sample_step (0: every
+                                //   frame with frame_count, as always)
+    float*   out_lin = nullptr; // when set, the end of a path stores its linear colour (finish_pixel's fin,
+                                //   before the sqrt) as 3 floats where out_rad would put the pixel, and
+                                //   neither out_rgba nor out_rad is written
 };
 
 // Host-side compact-scene build from the reference records; validates the
@@ -353,5 +361,23 @@ struct VarianceArgs {
     int           stage;        // option variance_stage: -1 = everything, 0 = the estimate alone (timing)
 };
 hipError_t launch_denoise_variance(const VarianceArgs& d, hipStream_t stream);
+
+// rt_samples.hip: folds the linear-colour frames of one samples launch into
+// the running sum, in frame order (rtamd.h rt_render_samples_device, DESIGN.md
+// §4k), enqueued on `stream`; validated arguments, nothing allocated.
+struct SamplesArgs {
+    size_t        n_px;         // pixels of a frame
+    const float*  slices;       // n_slices frames of 3 * n_px floats, one after another
+    int           n_slices;     // 1..kMaxBatch
+    int           load_sum;     // 1 = start from *sum, 0 = from slice 0 (sum is not read)
+    float*        sum;          // 3 * n_px floats
+    int           finish;       // 1 = the call's last chunk: also write the outputs
+    float         divisor;      // finish: the samples in the sum, an exact float
+    uchar4*       out_rgba;     // finish: nullable
+    float*        out_rad;      // finish: nullable
+    int           form;         // 0 = 16-byte accesses where every base and a frame's byte size allow them,
+                                //   1 = the scalar form (one pixel per lane)
+};
+hipError_t launch_samples_resolve(const SamplesArgs& r, hipStream_t stream);
 
 }  // namespace rtamd

@@ -338,6 +338,12 @@ struct PerDevice {
     // rt_render_temporal_variance: the pair of moments buffers behind the other parts of d_temporal holds,
     // at index temporal_last, the moments of the current history (false after a call that wrote none)
     bool         moments_valid = false;
+    // rt_render_samples: one allocation holding the running sum, the launches'
+    // workspace and the outputs, grown on demand; and how many samples of
+    // which frame size the sum holds (0: none)
+    char*        d_samples = nullptr;
+    size_t       samples_cap = 0;    // bytes
+    int          samples_held = 0, samples_w = 0, samples_h = 0;
 };
 
 static constexpr size_t kMaxOrders = 16;
@@ -454,6 +460,14 @@ struct rt_ctx {
     int  temporal_tile = 0;        // rt_temporal_device: 0 = the lane mapping measured faster, 1 = a wave on 64
                                    //   pixels of a row, 2 = on a 16x4 tile (rt_temporal.hip; same results)
     int  variance_stage = -1;      // rt_denoise_variance_device: 0 = enqueue the estimate alone (tools/variance_bench.py)
+    int  sample_frames = 16;       // rt_render_samples_device: sample frames per trace launch (1..kMaxBatch).
+                                   //   Config 3 at 16 samples per call, ms per sample: 1 frame per launch 0.360,
+                                   //   2 0.209, 4 0.149, 8 0.140, 16 0.134, windows within 0.3% of their medians
+                                   //   (profiles/samples)
+    int  samples_kernel = 0;       // its resolve: 0 = 16-byte accesses where the buffers allow, 1 = the scalar form
+                                   //   (rt_samples.hip; same results)
+    int  samples_stage = -1;       // 0 = enqueue its trace launches alone, 1 = its resolves alone
+                                   //   (tools/samples_bench.py; the outputs are meaningless); -1 = both
     int  split_bounce = 0;         // accel walk: paths alive at this bounce finish in a second kernel
                                    //   (0 = one kernel)
     int  split_pixels = kSplitPixelsDefault;   // split_bounce 0: a plain format-0 accel launch of at least this
@@ -932,7 +946,8 @@ static int set_schedule(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_
     a.coop_walk = p.scene.n_layouts ? 0 : ctx->coop_walk;
     a.coop_win = coop_window_of(ctx, p);
     a.block_waves = ctx->block_waves;
-    a.ext = ctx->ext | (ctx->new_sample ? kExtNewSample : 0);
+    // (a samples launch, sample_step set: the kernels' bit 16 whatever option new_sample says)
+    a.ext = ctx->ext | ((ctx->new_sample || a.sample_step) ? kExtNewSample : 0);
     a.solo_lanes = p.last_solo = solo_lanes_of(ctx, p.scene, a.coop_lanes, a.ext);
     a.scene.spheres = p.d_spheres;
     a.scene.n_spheres = (a.ext & kExtSpheres) ? p.n_spheres : 0;
@@ -940,7 +955,7 @@ static int set_schedule(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_
     a.sky_enabled = cam->sky_enabled;
     a.frame_count = cam->frame_count;
     a.accum = nullptr;
-    if ((a.ext & kExtNewSample) && !(a.ext & kExtAccumulate) && a.n_frames != 1) {
+    if ((a.ext & kExtNewSample) && !(a.ext & kExtAccumulate) && a.n_frames != 1 && !a.sample_step) {
         // (a launch carries one frame_count, its first camera's: the rule of the accumulation extension)
         set_error("option new_sample renders one frame per launch (a launch carries one frame_count)");
         return RT_ERR_INVALID_ARG;
@@ -1016,7 +1031,8 @@ static std::vector<uint64_t> launch_key(const TraceArgs& a, hipStream_t s) {
             (uint64_t)a.frame_count, P(a.accum), (uint64_t)a.walk, (uint64_t)a.block_waves, P(a.tile_order),
             (uint64_t)a.heavy_tiles, (uint64_t)(a.aux_stream != nullptr), (uint64_t)a.heavy_fused, P(a.heavy_px),
             (uint64_t)a.n_heavy_px, P(a.tile_mask), (uint64_t)a.coop_walk, (uint64_t)a.coop_win,
-            (uint64_t)a.split_bounce, P(a.q_slots), (uint64_t)a.q_queues, (uint64_t)a.q_cap};
+            (uint64_t)a.split_bounce, P(a.q_slots), (uint64_t)a.q_queues, (uint64_t)a.q_cap,
+            (uint64_t)a.sample_step, P(a.out_lin)};
     for (int f = 0; f < a.n_frames; ++f) {
         const CamF& c = a.cams[f];
         for (float v : {c.ox, c.oy, c.oz, c.lx, c.ly, c.lz, c.hx, c.hy, c.hz, c.vx, c.vy, c.vz}) k.push_back(F(v));
@@ -1301,6 +1317,7 @@ int rt_destroy(rt_ctx* ctx) {
         if (p.d_query) (void)hipFree(p.d_query);
         if (p.d_denoise) (void)hipFree(p.d_denoise);
         if (p.d_temporal) (void)hipFree(p.d_temporal);
+        if (p.d_samples) (void)hipFree(p.d_samples);
         if (p.d_rgba) (void)hipFree(p.d_rgba);
         if (p.d_rad) (void)hipFree(p.d_rad);
         if (p.ev0) (void)hipEventDestroy(p.ev0);
@@ -1513,6 +1530,7 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
     ctx->has_scene = true;
     ++ctx->scene_gen;
     for (PerDevice& p : ctx->dev) p.temporal_valid = false;   // rt_render_temporal starts a new sequence
+    for (PerDevice& p : ctx->dev) p.samples_held = 0;         // and rt_render_samples a new sum
     free_host_scene(&hs);
     return RT_OK;
 }
@@ -1551,6 +1569,7 @@ int rt_upload_spheres(rt_ctx* ctx, const float* spheres, int n_spheres) {
     }
     ++ctx->scene_gen;    // learned tile orders see the new work
     for (PerDevice& p : ctx->dev) p.temporal_valid = false;   // rt_render_temporal starts a new sequence
+    for (PerDevice& p : ctx->dev) p.samples_held = 0;         // and rt_render_samples a new sum
     return RT_OK;
 }
 
@@ -2523,6 +2542,190 @@ int rt_render_batch_device(rt_ctx* ctx, const rt_camera_ubo* cams, int n_frames,
     return RT_OK;
 }
 
+// ------------------------------------------------------------------ samples --
+// Several samples per pixel in one call (rtamd.h "samples"): a
+// whole-frame batch launch whose frames are consecutive samples of one camera,
+// each storing its linear colour, then rt_samples.hip's resolve on the same
+// stream.  Both samples calls check their arguments here.
+static int check_samples_args(const char* fn, rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height,
+                              int max_bounces, int n_samples) {
+    if (int rc = check_render_args(ctx, cam, width, height, max_bounces, fn)) return rc;
+    if (ctx->dev.size() != 1) {
+        set_error("%s: the context has %zu devices; samples are resolved on whole frames of one device", fn,
+                  ctx->dev.size());
+        return RT_ERR_INVALID_ARG;
+    }
+    if (ctx->ext & kExtAccumulate) {
+        set_error("%s: extensions bit 4 is set (the frame would be averaged twice)", fn);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (n_samples < 1 || n_samples > 65536) {
+        set_error("%s: n_samples must be in [1, 65536], got %d", fn, n_samples);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (cam->frame_count < 0) {
+        set_error("%s: frame_count (the first sample) must be >= 0, got %d", fn, cam->frame_count);
+        return RT_ERR_INVALID_ARG;
+    }
+    if ((int64_t)cam->frame_count + n_samples > (int64_t)1 << 24) {
+        set_error("%s: samples %d .. %lld reach past 2^24 (the divisor must stay an exact float)", fn,
+                  cam->frame_count, (long long)cam->frame_count + n_samples - 1);
+        return RT_ERR_INVALID_ARG;
+    }
+    return RT_OK;
+}
+
+// One trace launch of a samples call: samples first .. first + n_frames - 1 of
+// `cam` as the frames of a whole-frame batch launch, their linear colours one
+// frame after another at d_lin.  The launcher, the learned order and the
+// schedule are rt_render_batch_device's.  The order's key sees the camera
+// with frame_count 0: the sample index moves the jitter, not the tiles' cost,
+// so a call's chunks and later calls share one learned order.
+static int samples_trace(const rt_ctx* ctx, PerDevice& p, const rt_camera_ubo* cam, int first, int n_frames,
+                         int width, int height, int max_bounces, float* d_lin, hipStream_t s, bool count) {
+    TraceArgs a;
+    a.scene = p.scene;
+    rt_camera_ubo cams[kMaxBatch];
+    for (int f = 0; f < n_frames; ++f) {
+        cams[f] = *cam;
+        cams[f].frame_count = 0;
+        a.cams[f] = cam_from_ubo(cam);
+    }
+    a.n_frames = n_frames;
+    a.width = width; a.height = height; a.max_bounces = max_bounces;
+    a.x0 = 0; a.y0 = 0; a.tw = width; a.th = height;
+    a.band_h = height; a.band_stride = 1; a.band_off = 0;
+    a.band_list = nullptr;
+    a.list_stride = 0;
+    a.out_rgba = nullptr;
+    a.out_rad = nullptr;
+    a.sample_step = 1;
+    a.out_lin = d_lin;
+    a.counters = count ? p.d_counters : nullptr;
+    if (int rs = set_schedule(ctx, p, a, cams)) return rs;
+    a.frame_count = first;
+    if (int rl = launch(ctx, p, a, s)) return rl;
+    return learn_order(ctx, p, a, s);
+}
+
+int rt_render_samples_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                             int n_samples, void* d_workspace, size_t workspace_bytes, float* d_sum,
+                             void* d_out_rgba, float* d_out_radiance, void* stream, rt_stats* stats) {
+    const char* fn = "rt_render_samples_device";
+    if (int rc = check_samples_args(fn, ctx, cam, width, height, max_bounces, n_samples)) return rc;
+    if (!d_sum || !d_workspace) {
+        set_error("%s: %s is null", fn, d_sum ? "d_workspace" : "d_sum");
+        return RT_ERR_INVALID_ARG;
+    }
+    if (!d_out_rgba && !d_out_radiance) { set_error("%s: both outputs are null", fn); return RT_ERR_INVALID_ARG; }
+    const size_t px = (size_t)width * (size_t)height, frame_bytes = px * 12;
+    if (workspace_bytes < frame_bytes) {
+        set_error("%s: a workspace of %zu bytes cannot hold one frame (%zu bytes)", fn, workspace_bytes, frame_bytes);
+        return RT_ERR_INVALID_ARG;
+    }
+    if ((((uintptr_t)d_workspace | (uintptr_t)d_sum) & 15u) || (((uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
+        set_error("%s: d_workspace and d_sum must be 16-byte aligned, the outputs 4-byte", fn);
+        return RT_ERR_INVALID_ARG;
+    }
+    const int frames_ws = (int)std::min<size_t>((size_t)kMaxBatch, workspace_bytes / frame_bytes);
+    const struct { const void* p; size_t n; const char* name; } buf[4] = {
+        {d_workspace, (size_t)frames_ws * frame_bytes, "d_workspace"}, {d_sum, frame_bytes, "d_sum"},
+        {d_out_rgba, px * 4, "d_out_rgba"}, {d_out_radiance, frame_bytes, "d_out_radiance"}};
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (buf[i].p && buf[j].p && ranges_overlap(buf[i].p, buf[i].n, buf[j].p, buf[j].n)) {
+                set_error("%s: %s overlaps %s", fn, buf[j].name, buf[i].name);
+                return RT_ERR_INVALID_ARG;
+            }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the null stream
+    const int first = cam->frame_count;
+    if (stats) {
+        // the counting kernels add to the counters: zeroed once, they end as the call's totals
+        RT_HIP_CHECK(hipMemsetAsync(p.d_counters, 0, sizeof(Counters), s));
+        RT_HIP_CHECK(hipEventRecord(p.ev0, s));
+    }
+    for (int done = 0; done < n_samples;) {
+        const int c = std::min(std::min(ctx->sample_frames, frames_ws), n_samples - done);
+        if (ctx->samples_stage != 1)
+            if (int rt = samples_trace(ctx, p, cam, first + done, c, width, height, max_bounces,
+                                       static_cast<float*>(d_workspace), s, stats != nullptr))
+                return rt;
+        done += c;
+        if (ctx->samples_stage == 0) continue;
+        SamplesArgs r;
+        r.n_px = px;
+        r.slices = static_cast<const float*>(d_workspace);
+        r.n_slices = c;
+        r.load_sum = first + done - c > 0 ? 1 : 0;
+        r.sum = d_sum;
+        r.finish = done == n_samples ? 1 : 0;
+        r.divisor = (float)(first + n_samples);
+        r.out_rgba = static_cast<uchar4*>(d_out_rgba);
+        r.out_rad = d_out_radiance;
+        r.form = ctx->samples_kernel;
+        RT_HIP_CHECK(launch_samples_resolve(r, s));
+    }
+    if (stats) {
+        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
+        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
+        return collect_stats(ctx, p, (uint64_t)px * (uint64_t)n_samples, stats, false);
+    }
+    return RT_OK;
+}
+
+int rt_render_samples(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces, int n_samples,
+                      uint8_t* out_rgba, float* out_radiance, rt_stats* stats) {
+    const char* fn = "rt_render_samples";
+    if (int rc = check_samples_args(fn, ctx, cam, width, height, max_bounces, n_samples)) return rc;
+    if (!out_rgba && !out_radiance) { set_error("%s: both outputs are null", fn); return RT_ERR_INVALID_ARG; }
+    PerDevice& p = ctx->dev[0];
+    if (width != p.samples_w || height != p.samples_h) p.samples_held = 0;   // another frame size: a new sum
+    const int first = cam->frame_count;
+    if (first > 0 && first != p.samples_held) {
+        set_error("%s: frame_count %d continues a sum of %d samples, but the context holds %d samples of this "
+                  "%dx%d frame (frame_count 0 starts over)", fn, first, first, p.samples_held, width, height);
+        return RT_ERR_INVALID_ARG;
+    }
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    // the sum, the workspace of one launch's frames, RGBA8 and radiance, each part on a 256-byte boundary
+    const size_t px = (size_t)width * (size_t)height;
+    const auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t ws_bytes = (size_t)std::min(ctx->sample_frames, n_samples) * px * 12;
+    const size_t o_ws = up(px * 12), o_rgba = o_ws + up(ws_bytes), o_rad = o_rgba + up(px * 4),
+                 total = o_rad + up(px * 12);
+    if (total > p.samples_cap) {
+        char* grown = nullptr;
+        const hipError_t e = hipMalloc(&grown, total);
+        if (e != hipSuccess) {
+            set_error("%s: %zu bytes of frame buffers: %s", fn, total, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+        }
+        if (p.d_samples) {
+            RT_HIP_CHECK(hipStreamSynchronize(p.stream));   // (the call is synchronous: nothing in flight)
+            if (first > 0) RT_HIP_CHECK(hipMemcpy(grown, p.d_samples, px * 12, hipMemcpyDeviceToDevice));   // the sum
+            (void)hipFree(p.d_samples);
+        }
+        p.d_samples = grown;
+        p.samples_cap = total;
+    }
+    char* const base = p.d_samples;
+    p.samples_held = 0;                          // (a failure below leaves no half-made sum behind)
+    p.samples_w = width;
+    p.samples_h = height;
+    int rc = rt_render_samples_device(ctx, cam, width, height, max_bounces, n_samples, base + o_ws, ws_bytes,
+                                      reinterpret_cast<float*>(base), out_rgba ? base + o_rgba : nullptr,
+                                      out_radiance ? reinterpret_cast<float*>(base + o_rad) : nullptr, p.stream, stats);
+    if (rc) return rc;
+    if (out_rgba) RT_HIP_CHECK(hipMemcpyAsync(out_rgba, base + o_rgba, px * 4, hipMemcpyDeviceToHost, p.stream));
+    if (out_radiance)
+        RT_HIP_CHECK(hipMemcpyAsync(out_radiance, base + o_rad, px * 12, hipMemcpyDeviceToHost, p.stream));
+    RT_HIP_CHECK(hipStreamSynchronize(p.stream));
+    p.samples_held = first + n_samples;
+    return RT_OK;
+}
+
 int rt_render_batch_rect_device(rt_ctx* ctx, const rt_camera_ubo* cams, int n_frames, int width, int height,
                                 int max_bounces, int x0, int y0, int tile_w, int tile_h,
                                 void* d_out_rgba, void* d_out_radiance, void* stream, rt_stats* stats) {
@@ -2955,6 +3158,9 @@ static const Option kOptions[] = {
     in_range("denoise_pass", &rt_ctx::denoise_pass, -1, 5),
     in_range("temporal_tile", &rt_ctx::temporal_tile, 0, 2),
     in_range("variance_stage", &rt_ctx::variance_stage, -1, 0),
+    in_range("sample_frames", &rt_ctx::sample_frames, 1, kMaxBatch),
+    one_of("samples_kernel", &rt_ctx::samples_kernel, 0, 1),
+    in_range("samples_stage", &rt_ctx::samples_stage, -1, 1),
 };
 
 static const Option* find_option(const char* name) {

@@ -297,6 +297,14 @@ constexpr int kFeatExtBit = 16;   // = kFeatExt (defined with the other feature 
 // then the sqrt'd RGBA8 store (:235).
 template <int FEAT>
 __device__ __forceinline__ void finish_pixel(const TraceArgs& a, int lx, int ly, V3 fin) {
+    if ((FEAT & kFeatExtBit) && a.out_lin) {
+        // a samples launch: the linear colour itself, for rt_samples.hip to fold
+        float* lin = a.out_lin + 3 * ((size_t)ly * (size_t)a.tw + (size_t)lx);
+        lin[0] = fin.x;
+        lin[1] = fin.y;
+        lin[2] = fin.z;
+        return;
+    }
     if ((FEAT & kFeatExtBit) && (a.ext & kExtAccumulate)) {
         // extension: running sum of the linear colour, shown as sqrt(mean)
         float* acc = a.accum + 3 * ((size_t)ly * (size_t)a.tw + (size_t)lx);
@@ -1255,7 +1263,9 @@ void trace_simple(TraceArgs a) {
         const int x = a.x0 + lx, y = frame_row(a, fr_i, ly);
         if ((FEAT & kFeatExt) && (a.ext & (kExtAccumulate | kExtNewSample))) {
             // extension: a new sample per frame; frame 0 is the reference's seed (:164)
-            seed = (uint32_t)(y * a.width + x) + (uint32_t)a.frame_count * (uint32_t)(a.width * a.height);
+            // (a samples launch: frame f of the batch is sample frame_count + f)
+            seed = (uint32_t)(y * a.width + x) +
+                   (uint32_t)(a.frame_count + fr_i * a.sample_step) * (uint32_t)(a.width * a.height);
             primary_ray_seeded(a, fr_i, x, y, seed, o, d);
         } else {
             primary_ray(a, fr_i, x, y, seed, o, d);

@@ -45,13 +45,14 @@ EXPORTED = (
     "rt_temporal_moments_device", "rt_variance_default_params", "rt_denoise_variance_device",
     "rt_render_temporal_variance",
     "rt_learn_device", "rt_learn_copy",
+    "rt_samples_workspace_bytes", "rt_render_samples_device", "rt_render_samples",
 )
 
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
 # "src=" field is the first 16 hex digits of SHA-256 over them concatenated.
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
                  "csrc/rt_denoise.hip", "csrc/rt_denoise_history.hip", "csrc/rt_temporal.hip", "csrc/rt_variance.hip",
-                 "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h",
+                 "csrc/rt_samples.hip", "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h",
                  "csrc/accel_build.h", "../include/rtamd.h")
 
 
@@ -266,6 +267,10 @@ def lib() -> C.CDLL:
                                                       C.POINTER(VarianceParams), C.c_uint32, vp, vp, C.POINTER(Stats)]),
                 "rt_learn_device": (i32, [vp, vp, vp, i32, C.POINTER(LearnParams), vp, vp, vp, vp, vp]),
                 "rt_learn_copy": (i32, [vp, C.POINTER(LearnInfo), vp, vp, vp, vp, vp]),
+                "rt_samples_workspace_bytes": (sz, [i32, i32, i32]),
+                "rt_render_samples_device": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, i32, vp, sz, vp, vp, vp, vp,
+                                                   C.POINTER(Stats)]),
+                "rt_render_samples": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, i32, vp, vp, C.POINTER(Stats)]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)

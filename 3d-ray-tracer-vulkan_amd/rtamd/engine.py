@@ -399,6 +399,44 @@ class Renderer:
                    rad.ctypes.data if rad is not None else None, C.byref(st) if st is not None else None))
         return rgba, rad, (st.as_dict() if st is not None else None)
 
+    # --- samples (include/rtamd.h "samples") ---
+    @staticmethod
+    def samples_workspace_bytes(width: int, height: int, frames: int) -> int:
+        """Bytes of render_samples_device's workspace for `frames` sample
+        frames per launch (rt_samples_workspace_bytes; 0 for bad arguments)."""
+        return lib().rt_samples_workspace_bytes(width, height, frames)
+
+    def render_samples_device(self, camera, width: int, height: int, max_bounces: int, n_samples: int,
+                              d_workspace: Optional[int], workspace_bytes: int, d_sum: Optional[int],
+                              d_out_rgba: Optional[int] = None, d_out_radiance: Optional[int] = None,
+                              stream: Optional[int] = None, stats: bool = False):
+        """Enqueue samples camera.frame_count .. + n_samples - 1 of one whole
+        frame and their resolve between device buffers (raw device pointers;
+        rt_render_samples_device) on a HIP stream handle: d_sum keeps the
+        running sum of the linear colour (overwritten when frame_count is 0,
+        continued otherwise), the outputs receive sqrt(sum / samples) as
+        extension bit 4 would show it.  Asynchronous unless stats (the totals
+        over the samples)."""
+        st = Stats() if stats else None
+        check(lib().rt_render_samples_device(self._ctx, C.byref(_ubo(camera)), width, height, max_bounces, n_samples,
+                                             d_workspace, workspace_bytes, d_sum, d_out_rgba, d_out_radiance, stream,
+                                             C.byref(st) if st is not None else None))
+        return st.as_dict() if st is not None else None
+
+    def render_samples(self, camera, width: int, height: int, max_bounces: int = REFERENCE_MAX_BOUNCES,
+                       n_samples: int = 1, radiance: bool = False, stats: bool = False):
+        """n_samples samples per pixel in one call (rt_render_samples), into the
+        context's own sum: camera.frame_count 0 starts it over, k > 0 continues
+        a sum of exactly k samples.  Returns (rgba, radiance or None, stats
+        dict or None).  One device, extensions bit 4 off."""
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        rad = np.empty((height, width, 3), dtype=np.float32) if radiance else None
+        st = Stats() if stats else None
+        check(lib().rt_render_samples(self._ctx, C.byref(_ubo(camera)), width, height, max_bounces, n_samples,
+                                      rgba.ctypes.data, rad.ctypes.data if rad is not None else None,
+                                      C.byref(st) if st is not None else None))
+        return rgba, rad, (st.as_dict() if st is not None else None)
+
     # --- heavy-first learning diagnostics (include/rtamd.h rt_learn_device, rt_learn_copy) ---
     def learn_device(self, d_records: int, d_lanes: int, n_tiles: int, d_order: int, d_mask: int, d_hpix: int,
                      d_count: int, stream: Optional[int] = None, **params) -> None:

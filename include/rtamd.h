@@ -578,6 +578,65 @@ int rt_render_temporal_variance(rt_ctx* ctx, const rt_camera_ubo* cam, int width
                                 const rt_temporal_params* tparams, const rt_variance_params* vparams, uint32_t flags,
                                 uint8_t* out_rgba, float* out_radiance, rt_stats* stats);
 
+/* ---------------------------------------------------------------- samples -- */
+/* NON-REFERENCE: several samples per pixel in one call.  Extension bit 4
+ * averages one sample per launch; here one trace launch carries up to 16
+ * consecutive samples of a camera as the frames of a whole-frame batch launch
+ * (rt_render_batch_device's launcher, learned order and schedule), each
+ * storing its linear colour, and a resolve kernel on the same stream folds
+ * them into a running sum in sample order.
+ *
+ * Sample k runs over first .. first + n_samples - 1, first = cam->frame_count
+ * (the field that names the sample under bit 4).  Sample k of a pixel is the
+ * path option new_sample traces with frame_count = k (seed = y * W + x +
+ * (uint32) k * (uint32) (W * H)); c_k = its linear colour, the value before
+ * the sqrt.  d_sum (width*height*3 floats, 16-byte aligned, required): for
+ * first == 0 it is overwritten, s = c_0 (never read: it may hold anything);
+ * for first > 0 it is read, s = d_sum + c_first; then s = s + c_k per channel
+ * in increasing k, one rounded add each.  fin = s / (float)(first + n_samples)
+ * and g = sqrt(fin): d_out_radiance (width*height*3 floats) receives g,
+ * d_out_rgba (width*height*4 bytes) g as the render quantises it, alpha 255;
+ * at least one of the two.  Sum, radiance and RGBA8 equal extension bit 4's
+ * after frames 0 .. first + n_samples - 1, bit for bit.  Extension bits 1, 2
+ * and 8 apply as to any render; bit 4 set is RT_ERR_INVALID_ARG (the frame
+ * would be averaged twice); option new_sample is neither read nor changed.
+ * The contract, operation by operation in IEEE binary32, is DESIGN.md §4k.
+ * Added at ABI version 6 without a bump: no existing struct or argument list
+ * changed.
+ *
+ * d_workspace: workspace_bytes bytes of scratch, 16-byte aligned, holding the
+ * linear colours of one launch's frames: at least one frame
+ * (rt_samples_workspace_bytes(width, height, 1)).  A launch traces
+ * min(option "sample_frames", the frames the workspace holds, the samples
+ * left) samples and is resolved before the next.  Stream and stats as
+ * rt_render_tile_device: asynchronous unless stats is given; stats = the
+ * totals over the samples, pixels = width*height*n_samples, ms = the device
+ * time from the first trace launch to the last resolve.  On device 0 of a
+ * one-device context.  RT_ERR_INVALID_ARG: n_samples outside 1..65536, first
+ * < 0, first + n_samples > 2^24 (the divisor stays an exact float), a null
+ * d_sum or workspace, both outputs null, a workspace that cannot hold one
+ * frame, a misaligned buffer (the outputs: 4-byte), any overlap between the
+ * workspace, the sum and the outputs, a context of several devices. */
+
+/* bytes of scratch for `frames` sample frames of width x height:
+   frames * width * height * 12 (0 for a bad size or frames outside 1..16).  Pure host code. */
+size_t rt_samples_workspace_bytes(int width, int height, int frames);
+int rt_render_samples_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                             int n_samples, void* d_workspace, size_t workspace_bytes,
+                             float* d_sum, void* d_out_rgba, float* d_out_radiance,
+                             void* stream, rt_stats* stats);
+/* The synchronous host form, into HOST memory (at least one of out_rgba and
+ * out_radiance).  The workspace (option "sample_frames" frames at most) and
+ * the sum belong to the context, grow on demand and are freed by rt_destroy.
+ * cam->frame_count == 0 starts the sum over; frame_count == k > 0 continues it
+ * and the context must hold exactly k samples of that frame size, otherwise
+ * RT_ERR_INVALID_ARG with a message that says how many it holds (a Java host
+ * with n samples per call advances its frameCount by n).  The sum is dropped
+ * by rt_upload_scene, rt_upload_spheres and a different frame size.  Same
+ * refusals as the device form. */
+int rt_render_samples(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
+                      int n_samples, uint8_t* out_rgba, float* out_radiance, rt_stats* stats);
+
 /* Schedule options (no effect on results, which are identical for every
  * setting):
  *   "kernel"        0 only: the one kernel, one lane per pixel (the
@@ -821,6 +880,21 @@ int rt_render_temporal_variance(rt_ctx* ctx, const rt_camera_ubo* cam, int width
  *                   its passes (2 = tiled at step 1, plain elsewhere; its own
  *                   choice at 0); with "denoise_pass" i only
  *                   pass i is enqueued, without the estimate
+ *   "sample_frames" rt_render_samples_device: the sample frames per trace
+ *                   launch, 1..16, default 16 (the fastest measured: config 3
+ *                   0.134 ms per sample against 0.149 at 4 and 0.360 at 1,
+ *                   DESIGN.md §4k); a launch also takes no more than the
+ *                   workspace holds and than the samples left.
+ *                   rt_render_samples' workspace holds this many frames (12
+ *                   bytes per pixel each) or the call's samples if fewer
+ *   "samples_kernel" its resolve: 0 (default) = 16-byte loads and stores
+ *                   where a frame's bytes and every buffer lie on the 16-byte
+ *                   grid, else one pixel per lane; 1 = always the latter.
+ *                   Same results; 1 is for tests and tools/samples_bench.py
+ *   "samples_stage" rt_render_samples_device: 0 = only its trace launches are
+ *                   enqueued, 1 = only its resolves, on whatever the workspace
+ *                   holds (tools/samples_bench.py times them this way; the
+ *                   outputs are meaningless); -1 (default) = both
  *   "extensions"    NON-REFERENCE features, bits (default 0 = the reference's
  *                   shader exactly):
  *                   1 = honour sky_enabled (@68): a miss is black when it is 0
