@@ -133,56 +133,56 @@ constexpr int kMaxSplitQueues = 1024;   // option split_queues
 
 struct TraceArgs {
     DevScene scene;
-    CamF     cams[kMaxBatch];   // frame f of the batch is seen through cams[f]
-    int      n_frames;          // frames in the launch (1..kMaxBatch): the same rows of each
-    int      tiles_y;           // wave-tile rows per frame (launcher-internal: ceil(th / tile height))
-    int      width, height;     // full frame
-    int      max_bounces;
-    int      x0, y0, tw, th;    // columns [x0, x0+tw); th local rows per frame
+    CamF     cams[kMaxBatch] = {}; // frame f of the batch is seen through cams[f]
+    int      n_frames = 0;      // frames in the launch (1..kMaxBatch): the same rows of each
+    int      tiles_y = 0;       // wave-tile rows per frame (launcher-internal: ceil(th / tile height))
+    int      width = 0, height = 0; // full frame
+    int      max_bounces = 0;
+    int      x0 = 0, y0 = 0, tw = 0, th = 0; // columns [x0, x0+tw); th local rows per frame
     // Local row ly is frame row y0 + ((ly / band_h) * band_stride + band_off) * band_h + ly % band_h:
     // a plain tile is band_h = th, band_stride = 1, band_off = 0; rank r of N
     // interleaved 16-row bands is band_h = 16, band_stride = N, band_off = r.
     // With band_list (device, nullable) it is band_list[ly / band_h] * band_h + ly % band_h; with
     // list_stride > 0 frame f reads its own list at band_list + f * list_stride, whose -1 entries
     // (trailing padding) and rows past the frame are not traced.
-    int      band_h, band_stride, band_off;
-    const int* band_list;
+    int      band_h = 0, band_stride = 1, band_off = 0;
+    const int* band_list = nullptr;
     // Outputs: n_frames x th x tw pixels, frame f's local row ly at row f * th + ly
-    uchar4*  out_rgba;          // nullable
-    float*   out_rad;           // 3 floats per pixel, nullable
-    Counters* counters;         // nullable
-    int      wave_tile;         // wave tile (8<<s) x (8>>s), s in 0..3
-    unsigned long long* diag;   // diagnostics: 8 words per wave, or null
-    int      coop_lanes;        // finish a wave's walks cooperatively once at most
+    uchar4*  out_rgba = nullptr; // nullable
+    float*   out_rad = nullptr; // 3 floats per pixel, nullable
+    Counters* counters = nullptr; // nullable
+    int      wave_tile = 0;     // wave tile (8<<s) x (8>>s), s in 0..3
+    unsigned long long* diag = nullptr; // diagnostics: 8 words per wave, or null
+    int      coop_lanes = 0;    // finish a wave's walks cooperatively once at most
                                 //   this many lanes are still walking (0 = never)
-    int      solo_lanes;        // format-0 accel walk without the cooperative tail: once at most this many
+    int      solo_lanes = 0;    // format-0 accel walk without the cooperative tail: once at most this many
                                 //   lanes of a wave are still walking, their walks are finished one ray at a
                                 //   time through the scalar cache (solo_walk, rt_trace.hip; 0 = never)
-    int      ext;               // non-reference extensions, kExt* bits (0 = the reference)
-    int      sky_enabled;       // CameraUBO.sky_enabled (@68), read only with kExtSkyToggle
-    int      frame_count;       // CameraUBO.frame_count (@64), read only with kExtAccumulate / kExtNewSample
-    float*   accum;             // kExtAccumulate: running linear-colour sums, 3 floats per pixel (tw*th)
-    int      walk;              // 0 = one node per step (nodes/leafs), 2 = the same software-pipelined
+    int      ext = 0;           // non-reference extensions, kExt* bits (0 = the reference)
+    int      sky_enabled = 1;   // CameraUBO.sky_enabled (@68), read only with kExtSkyToggle
+    int      frame_count = 0;   // CameraUBO.frame_count (@64), read only with kExtAccumulate / kExtNewSample
+    float*   accum = nullptr;   // kExtAccumulate: running linear-colour sums, 3 floats per pixel (tw*th)
+    int      walk = 0;          // 0 = one node per step (nodes/leafs), 2 = the same software-pipelined
                                 //   over the compact records (nodes2/leafs2; default)
-    int      block_waves;       // waves per workgroup, 4 (256 threads) or 1 (64 threads)
-    const int* tile_order;      // block_waves 1: workgroup k traces wave tile tile_order[k] (or k)
-    int      tiles_x;           // with tile_order (1-D grid): wave tiles per tile row
-    int      split_n;           // with tile_order: the first split_n tiles of the order are traced
+    int      block_waves = 0;   // waves per workgroup, 4 (256 threads) or 1 (64 threads)
+    const int* tile_order = nullptr; // block_waves 1: workgroup k traces wave tile tile_order[k] (or k)
+    int      tiles_x = 0;       // with tile_order (1-D grid): wave tiles per tile row
+    int      split_n = 0;       // with tile_order: the first split_n tiles of the order are traced
                                 //   one pixel per wave (64 workgroups each; launcher-internal)
-    int      heavy_tiles;       // with tile_order: the first heavy_tiles tiles run in that split
+    int      heavy_tiles = 0;   // with tile_order: the first heavy_tiles tiles run in that split
                                 //   mode as a concurrent launch on aux_stream (fork ev_fork, join ev_join)
-    int      heavy_fused;       // with heavy_tiles: 1 = the heavy tiles' one-pixel workgroups come
+    int      heavy_fused = 0;   // with heavy_tiles: 1 = the heavy tiles' one-pixel workgroups come
                                 //   first in the same launch (option heavy_stream 2), no aux stream
-    const int* heavy_px;        // fused, with tile_order: heavy pixels (tile * 64 + lane), traced one
-    int      n_heavy_px;        //   per wave by the first n_heavy_px workgroups of the launch
-    const unsigned long long* tile_mask;   // per tile: the lanes (heavy pixels) its tile wave skips, or null
-    unsigned* diag_lane;        // learning launch: each pixel's walk length (64 per wave), or null
-    hipStream_t aux_stream;
-    hipEvent_t ev_fork, ev_join;
-    int      coop_walk;         // cooperative tail: 0 = 64-node preorder windows (coop_walk),
+    const int* heavy_px = nullptr; // fused, with tile_order: heavy pixels (tile * 64 + lane), traced one
+    int      n_heavy_px = 0;    //   per wave by the first n_heavy_px workgroups of the launch
+    const unsigned long long* tile_mask = nullptr; // per tile: the lanes (heavy pixels) its tile wave skips, or null
+    unsigned* diag_lane = nullptr; // learning launch: each pixel's walk length (64 per wave), or null
+    hipStream_t aux_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int      coop_walk = 0;     // cooperative tail: 0 = 64-node preorder windows (coop_walk),
                                 //   1 = preorder frontier (frontier_walk)
     int      coop_win = 64;     // coop_walk's window: 64 or 32 slots (option coop_window)
-    int      list_stride;       // band_list per frame: frame f's at band_list + f * list_stride
+    int      list_stride = 0;   // band_list per frame: frame f's at band_list + f * list_stride
                                 //   (0 = one list for every frame of the launch)
     const int* row_off = nullptr;   // per frame: its first output row (null: f * th); device memory
     // Split launch (options split_bounce / split_pixels, accel walk; DESIGN.md

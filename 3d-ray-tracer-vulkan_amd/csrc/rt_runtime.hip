@@ -434,7 +434,6 @@ struct rt_ctx {
                                    //   one-pixel waves (CUs x 24 / 64 tiles)
     int  async_slots = 4;          // rt_render_async: frames in flight per device, each on its own stream
     int  copy_streams = 1;         // rt_render_async, one device: the readback split over this many copy streams (2 measured slower)
-    int  in_async = 0;             // set while rt_render_async plans a launch: its frames in flight
     int  concurrent_launches = 1;  // launches of similar work the caller keeps in flight on a device at once
                                    //   (the heavy-tile bulk estimate counts this launch's work that many times)
     int  learn_cost = 1;           // heavy_first cost: 0 = lockstep steps + 2 x coop windows, 1 = wave duration
@@ -518,8 +517,9 @@ static void free_scene(PerDevice& p) {
 
 // Launches of similar work on a device at once, for the heavy-pixel bar: the
 // caller's statement (option concurrent_launches), or rt_render_async's own
-// frames in flight.
-static int concurrency(const rt_ctx* ctx) { return std::max(ctx->concurrent_launches, ctx->in_async); }
+// frames in flight (RenderLaunch::in_flight).  enqueue_render works it out once
+// per launch and hands it to the planning and the learning.
+static int concurrency(const rt_ctx* ctx, int in_flight) { return std::max(ctx->concurrent_launches, in_flight); }
 
 // Heavy-first dispatch (option heavy_first, kernel 0 with one-wave
 // workgroups): the first launch of a given frame geometry + camera + scene
@@ -528,19 +528,10 @@ static int concurrency(const rt_ctx* ctx) { return std::max(ctx->concurrent_laun
 // order, so the waves that set the frame time start first.  Results do not
 // change (a tile's pixels and seeds are the same whichever workgroup traces
 // it); the learning launch ends with a stream synchronisation.
+// (a arrives with TraceArgs' defaults in every field of the order and the heavy
+// work: raster order, nothing split out)
 static int plan_order(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_camera_ubo* cams,
-                      const std::vector<int>* bands) {
-    a.tile_order = nullptr;
-    a.tiles_x = 0;
-    a.split_n = 0;
-    a.heavy_tiles = 0;
-    a.aux_stream = nullptr;
-    a.heavy_fused = 0;
-    a.heavy_px = nullptr;
-    a.n_heavy_px = 0;
-    a.tile_mask = nullptr;
-    a.diag_lane = nullptr;
-    a.ev_fork = a.ev_join = nullptr;
+                      const std::vector<int>* bands, int concurrent) {
     p.last_heavy = 0;
     p.last_heavy_px = 0;
     if (!ctx->heavy_first || a.block_waves != 1) return RT_OK;
@@ -553,7 +544,7 @@ static int plan_order(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_ca
     // device has no heavy tiles, one learned on the host does)
     std::vector<int> geo = {a.width, a.height, a.max_bounces, a.x0, a.y0, a.tw, a.th, a.band_h, a.band_stride,
                             a.band_off, a.wave_tile, a.ext, a.coop_lanes, a.solo_lanes, a.walk, ctx->learn_cost, ctx->order_split,
-                            ctx->heavy_factor, concurrency(ctx), ctx->heavy_cap, ctx->heavy_pixel_factor,
+                            ctx->heavy_factor, concurrent, ctx->heavy_cap, ctx->heavy_pixel_factor,
                             a.n_frames, bands ? (int)bands->size() : -1, a.list_stride, ctx->order_frames,
                             ctx->heavy_stream, ctx->heavy_pixels, ctx->heavy_tiles, ctx->learn_device,
                             ctx->xcd_order, ctx->accel_octants};
@@ -718,9 +709,9 @@ static int plan_order(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_ca
 // The device path of learn_order: a pending order whose buffers the learning
 // kernels fill on stream s; the heavy-pixel count follows into pinned memory
 // and an event marks it ready (poll_learning).
-static int learn_order_device(const rt_ctx* ctx, PerDevice& p, hipStream_t s) {
+static int learn_order_device(const rt_ctx* ctx, PerDevice& p, hipStream_t s, int concurrent) {
     const size_t n = p.learning_n;
-    const int conc = std::max(1, concurrency(ctx));
+    const int conc = std::max(1, concurrent);
     const int cap = std::max(1, p.n_cu * kResidentPerCu * ctx->heavy_cap / 100 / conc);
     const size_t need = learn_scratch_bytes((int)n);
     // Out of device memory for the learning's scratch (it sorts a 64-bit key
@@ -791,11 +782,11 @@ static int learn_order_device(const rt_ctx* ctx, PerDevice& p, hipStream_t s) {
 // A tile's cost is its wave's lockstep walk iterations plus twice its
 // cooperative windows (diag record words 4 and 5): the length of the wave's
 // dependent chain, free of when the wave happened to run.
-static int learn_order(const rt_ctx* ctx, PerDevice& p, const TraceArgs& a, hipStream_t s) {
-    const int learn_cost = ctx->learn_cost, concurrent = concurrency(ctx);
+static int learn_order(const rt_ctx* ctx, PerDevice& p, const TraceArgs& a, hipStream_t s, int concurrent) {
+    const int learn_cost = ctx->learn_cost;
     const double heavy_factor = ctx->heavy_factor / 100.0;
     if (!a.diag || a.diag != p.d_learn) return RT_OK;
-    if (p.learning_device) return learn_order_device(ctx, p, s);
+    if (p.learning_device) return learn_order_device(ctx, p, s, concurrent);
     const size_t n = p.learning_n;
     RT_HIP_CHECK(hipStreamSynchronize(s));
     std::vector<unsigned long long> rec(n * kDiagWords);
@@ -937,8 +928,9 @@ static int solo_lanes_of(const rt_ctx* ctx, const DevScene& sc, int coop_lanes, 
     return ctx->solo_lanes >= 0 ? ctx->solo_lanes : 1;
 }
 
+// new_sample: option new_sample, or the launch's own (RenderLaunch::new_sample).
 static int set_schedule(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_camera_ubo* cam,
-                        const std::vector<int>* bands = nullptr) {
+                        const std::vector<int>* bands, bool new_sample, int concurrent) {
     a.wave_tile = wave_tile_of(ctx, p);
     // (the cooperative tail walks 32-B slots: not over half-format accel records)
     a.coop_lanes = (p.scene.half || p.scene.wide) ? 0 : ctx->coop_lanes >= 0 ? ctx->coop_lanes : (p.scene.n_layouts ? 0 : 1);
@@ -947,14 +939,13 @@ static int set_schedule(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_
     a.coop_win = coop_window_of(ctx, p);
     a.block_waves = ctx->block_waves;
     // (a samples launch, sample_step set: the kernels' bit 16 whatever option new_sample says)
-    a.ext = ctx->ext | ((ctx->new_sample || a.sample_step) ? kExtNewSample : 0);
+    a.ext = ctx->ext | ((new_sample || a.sample_step) ? kExtNewSample : 0);
     a.solo_lanes = p.last_solo = solo_lanes_of(ctx, p.scene, a.coop_lanes, a.ext);
     a.scene.spheres = p.d_spheres;
     a.scene.n_spheres = (a.ext & kExtSpheres) ? p.n_spheres : 0;
     a.scene.oct_mask = ctx->accel_octants;
     a.sky_enabled = cam->sky_enabled;
     a.frame_count = cam->frame_count;
-    a.accum = nullptr;
     if ((a.ext & kExtNewSample) && !(a.ext & kExtAccumulate) && a.n_frames != 1 && !a.sample_step) {
         // (a launch carries one frame_count, its first camera's: the rule of the accumulation extension)
         set_error("option new_sample renders one frame per launch (a launch carries one frame_count)");
@@ -984,7 +975,6 @@ static int set_schedule(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_
         }
         a.accum = p.d_accum;
     }
-    a.diag = nullptr;
     if (ctx->diag) {
         // 8 words per wave (+ 63 per heavy tile traced one pixel per wave)
         const int tw_w = 8 << a.wave_tile, th_w = 8 >> a.wave_tile;
@@ -1006,7 +996,7 @@ static int set_schedule(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, const rt_
         p.diag_used = words;
         a.diag = p.d_diag;
     }
-    return plan_order(ctx, p, a, cam, bands);
+    return plan_order(ctx, p, a, cam, bands, concurrent);
 }
 
 // Option graph: a plain kernel-0 launch (no counters, no diagnostics) is
@@ -1597,6 +1587,17 @@ static int check_render_args(rt_ctx* ctx, const rt_camera_ubo* cam, int width, i
     return RT_OK;
 }
 
+// The batch calls: the same, then the frames of one launch.
+static int check_batch_args(rt_ctx* ctx, const rt_camera_ubo* cams, int n_frames, int width, int height,
+                            int max_bounces, const char* fn) {
+    if (int rc = check_render_args(ctx, cams, width, height, max_bounces, fn)) return rc;
+    if (n_frames < 1 || n_frames > kMaxBatch) {
+        set_error("%s: n_frames must be in [1, %d], got %d", fn, kMaxBatch, n_frames);
+        return RT_ERR_INVALID_ARG;
+    }
+    return RT_OK;
+}
+
 static int ensure_out(PerDevice& p, size_t pixels, bool rad) {
     if (pixels > p.out_cap || (rad && !p.d_rad)) {
         if (p.d_rgba) (void)hipFree(p.d_rgba);
@@ -1611,7 +1612,177 @@ static int ensure_out(PerDevice& p, size_t pixels, bool rad) {
     return RT_OK;
 }
 
-static int collect_stats(const rt_ctx* ctx, PerDevice& p, uint64_t pixels, rt_stats* stats, bool accumulate);
+// ------------------------------------------------------------------- stats --
+// A counting launch's bracket on stream s: the device's counters start from
+// zero and ev0 .. ev1 time what runs between them.  stats_begin opens it; the
+// code that enqueued the last counted work records ev1; stats_end (any call
+// that takes an rt_stats, which may be null) waits for it and reads both.
+static int collect_stats(PerDevice& p, uint64_t pixels, rt_stats* stats, bool accumulate) {
+    Counters c;
+    RT_HIP_CHECK(hipMemcpy(&c, p.d_counters, sizeof c, hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    RT_HIP_CHECK(hipEventElapsedTime(&ms, p.ev0, p.ev1));
+    if (!accumulate) std::memset(stats, 0, sizeof *stats);
+    stats->pixels += pixels;
+    stats->segments += c.segments;
+    stats->node_visits += c.node_visits;
+    stats->tri_tests += c.tri_tests;
+    stats->mat_reads += c.mat_reads;
+    if (ms > stats->ms) stats->ms = ms;
+    return RT_OK;
+}
+
+static int stats_begin(PerDevice& p, hipStream_t s) {
+    RT_HIP_CHECK(hipMemsetAsync(p.d_counters, 0, sizeof(Counters), s));
+    RT_HIP_CHECK(hipEventRecord(p.ev0, s));   // the timing events exist for stats only
+    return RT_OK;
+}
+
+static int stats_end(PerDevice& p, uint64_t pixels, rt_stats* stats) {
+    if (!stats) return RT_OK;
+    RT_HIP_CHECK(hipEventSynchronize(p.ev1));
+    return collect_stats(p, pixels, stats, false);
+}
+
+// The filters' `double* ms` (no counters): the time on stream s since the caller recorded ev0.
+static int elapsed_ms(PerDevice& p, hipStream_t s, double* ms) {
+    RT_HIP_CHECK(hipEventRecord(p.ev1, s));
+    RT_HIP_CHECK(hipEventSynchronize(p.ev1));
+    float t = 0.0f;
+    RT_HIP_CHECK(hipEventElapsedTime(&t, p.ev0, p.ev1));
+    *ms = (double)t;
+    return RT_OK;
+}
+
+// A valid call with no pixel to trace: nothing is enqueued.
+static int nothing_to_trace(rt_stats* stats) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    return RT_OK;
+}
+
+// ------------------------------------------------------------------ launch --
+// A band list on the device (rt_render_batch_device), uploaded once per
+// distinct list and kept for the context's lifetime (a launch in flight may
+// still read it); past kMaxBandLists the device is drained and they are
+// dropped.
+static constexpr size_t kMaxBandLists = 256;
+
+static int device_band_list(PerDevice& p, const std::vector<int>& bands, const int** out) {
+    for (const auto& l : p.band_lists)
+        if (l.bands == bands) { *out = l.d; return RT_OK; }
+    if (p.band_lists.size() >= kMaxBandLists) {
+        RT_HIP_CHECK(hipDeviceSynchronize());
+        for (auto& l : p.band_lists) (void)hipFree(l.d);
+        p.band_lists.clear();
+    }
+    int* d = nullptr;
+    RT_HIP_CHECK(hipMalloc(&d, std::max<size_t>(1, bands.size()) * sizeof(int)));
+    const hipError_t e = hipMemcpy(d, bands.data(), bands.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        RT_HIP_CHECK(e);
+    }
+    p.band_lists.push_back(PerDevice::BandList{bands, d});
+    *out = d;
+    return RT_OK;
+}
+
+// One render launch as its entry point states it: the same rows and columns
+// of n_frames frames, frame f seen through cams[f], the outputs holding the
+// frames one after another (n_frames x rows x tw pixels).  The rows of a
+// frame are the band_h-row bands b with b mod band_stride == band_off, moved
+// down by y0 (a tile or rectangle: one band of its own height at y0); or,
+// with `bands`, the listed bands: one list for every frame, or (list_stride >
+// 0) list_stride entries per frame, -1 padded, after which (row_offsets) each
+// frame's first output row follows.
+struct RenderLaunch {
+    const rt_camera_ubo* cams = nullptr;
+    int      n_frames = 1;
+    int      width = 0, height = 0, max_bounces = 0;
+    int      x0 = 0, tw = 0;            // columns [x0, x0 + tw)
+    int      y0 = 0;
+    int      band_h = 0, band_stride = 1, band_off = 0;
+    const std::vector<int>* bands = nullptr;
+    int      list_stride = 0;
+    bool     row_offsets = false;
+    int      rows = 0;                  // local rows per frame
+    uchar4*  rgba = nullptr;            // nullable
+    float*   rad = nullptr;             // nullable
+    // A samples launch (rt_render_samples_device) instead: the frames are samples first_sample,
+    // first_sample + 1, ... of cams[0], each storing its linear colour at lin
+    float*   lin = nullptr;
+    int      first_sample = 0;
+    bool     count = false;             // the counting build, bracketed for stats_end
+    bool     new_sample = false;        // kExtNewSample for this launch, whatever option new_sample says
+    int      in_flight = 0;             // rt_render_async: its frames in flight (see concurrency)
+};
+
+// A launch over every column of the frames; its entry point names the rows and the outputs.
+static RenderLaunch frame_launch(const rt_camera_ubo* cams, int n_frames, int width, int height, int max_bounces) {
+    RenderLaunch l;
+    l.cams = cams; l.n_frames = n_frames;
+    l.width = width; l.height = height; l.max_bounces = max_bounces;
+    l.tw = width;
+    return l;
+}
+
+// Enqueues the launch on stream s: the one place that turns a description
+// into kernel arguments, plans the schedule and learns the order.
+static int enqueue_render(const rt_ctx* ctx, PerDevice& p, const RenderLaunch& l, hipStream_t s) {
+    TraceArgs a;
+    a.scene = p.scene;
+    a.n_frames = l.n_frames;
+    a.width = l.width; a.height = l.height; a.max_bounces = l.max_bounces;
+    a.x0 = l.x0; a.y0 = l.y0; a.tw = l.tw; a.th = l.rows;
+    a.band_h = l.band_h; a.band_stride = l.band_stride; a.band_off = l.band_off;
+    if (l.bands) {
+        if (int rb = device_band_list(p, *l.bands, &a.band_list)) return rb;
+        a.list_stride = l.list_stride;
+        if (l.row_offsets) a.row_off = a.band_list + (size_t)l.n_frames * l.list_stride;
+    }
+    a.out_rgba = l.rgba;
+    a.out_rad = l.rad;
+    // The cameras the kernels see, and the ones the learned order's key sees.
+    // A samples launch's key sees its camera with frame_count 0: the sample
+    // index moves the jitter, not the tiles' cost, so a call's chunks and
+    // later calls share one learned order.
+    const rt_camera_ubo* key_cams = l.cams;
+    rt_camera_ubo sample_cams[kMaxBatch];
+    for (int f = 0; f < l.n_frames; ++f) a.cams[f] = cam_from_ubo(l.lin ? l.cams : l.cams + f);
+    if (l.lin) {
+        for (int f = 0; f < l.n_frames; ++f) {
+            sample_cams[f] = *l.cams;
+            sample_cams[f].frame_count = 0;
+        }
+        key_cams = sample_cams;
+        a.sample_step = 1;
+        a.out_lin = l.lin;
+    }
+    // counters before set_schedule: a counting launch must not become the
+    // (non-counting) learning launch of the heavy-first order
+    a.counters = l.count ? p.d_counters : nullptr;
+    const int concurrent = concurrency(ctx, l.in_flight);
+    if (int rs = set_schedule(ctx, p, a, key_cams, l.bands, ctx->new_sample || l.new_sample, concurrent)) return rs;
+    if (l.lin) a.frame_count = l.first_sample;
+    // (a samples call counts over all its launches and resolves: its own bracket)
+    const bool bracket = l.count && !l.lin;
+    if (bracket)
+        if (int rb = stats_begin(p, s)) return rb;
+    if (int rl = launch(ctx, p, a, s)) return rl;
+    if (int ro = learn_order(ctx, p, a, s, concurrent)) return ro;
+    if (bracket) RT_HIP_CHECK(hipEventRecord(p.ev1, s));
+    return RT_OK;
+}
+
+// The single-device render calls past their checks: the launch on device 0 and
+// the caller's stream (NULL = the null stream), then the stats of its pixels.
+static int render_on_stream(rt_ctx* ctx, RenderLaunch& l, uint64_t pixels, void* stream, rt_stats* stats) {
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    l.count = stats != nullptr;
+    if (int rc = enqueue_render(ctx, p, l, static_cast<hipStream_t>(stream))) return rc;
+    return stats_end(p, pixels, stats);
+}
 
 int rt_render_tile_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height,
                           int max_bounces, int x0, int y0, int tile_w, int tile_h,
@@ -1623,36 +1794,12 @@ int rt_render_tile_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int 
                   x0, y0, tile_w, tile_h, width, height);
         return RT_ERR_INVALID_ARG;
     }
-    PerDevice& p = ctx->dev[0];
-    RT_HIP_CHECK(hipSetDevice(p.device));
-    hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the null stream
-    TraceArgs a;
-    a.scene = p.scene;
-    a.cams[0] = cam_from_ubo(cam);
-    a.n_frames = 1;
-    a.width = width; a.height = height; a.max_bounces = max_bounces;
-    a.x0 = x0; a.y0 = y0; a.tw = tile_w; a.th = tile_h;
-    a.band_h = tile_h; a.band_stride = 1; a.band_off = 0;
-    a.band_list = nullptr;
-    a.list_stride = 0;
-    a.out_rgba = static_cast<uchar4*>(d_out_rgba);
-    a.out_rad = static_cast<float*>(d_out_radiance);
-    // counters before set_schedule: a counting launch must not become the
-    // (non-counting) learning launch of the heavy-first order
-    a.counters = stats ? p.d_counters : nullptr;
-    if (int rs = set_schedule(ctx, p, a, cam)) return rs;
-    if (stats) {
-        RT_HIP_CHECK(hipMemsetAsync(p.d_counters, 0, sizeof(Counters), s));
-        RT_HIP_CHECK(hipEventRecord(p.ev0, s));
-    }
-    if (int rl = launch(ctx, p, a, s)) return rl;
-    if (int ro = learn_order(ctx, p, a, s)) return ro;
-    if (stats) {
-        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        return collect_stats(ctx, p, (uint64_t)tile_w * (uint64_t)tile_h, stats, false);
-    }
-    return RT_OK;
+    RenderLaunch l = frame_launch(cam, 1, width, height, max_bounces);
+    l.x0 = x0; l.tw = tile_w;
+    l.y0 = y0; l.band_h = tile_h; l.rows = tile_h;
+    l.rgba = static_cast<uchar4*>(d_out_rgba);
+    l.rad = static_cast<float*>(d_out_radiance);
+    return render_on_stream(ctx, l, (uint64_t)tile_w * (uint64_t)tile_h, stream, stats);
 }
 
 // ------------------------------------------------------------------ queries --
@@ -1675,45 +1822,21 @@ static int run_query(rt_ctx* ctx, PerDevice& p, TraceArgs& a, uint64_t n, unsign
     a.scene.spheres = nullptr;                           // queries see triangles only
     a.scene.n_spheres = 0;
     a.scene.oct_mask = ctx->accel_octants;
+    // what differs from TraceArgs' defaults (no outputs, order, heavy work, extension or diagnostics;
+    // one band, 64-slot windows, sky on): one frame, one segment per ray, the walk-2 records
     a.n_frames = 1;
     a.max_bounces = 1;
-    a.band_stride = 1; a.band_off = 0;
-    a.band_list = nullptr;
-    a.list_stride = 0;
-    a.out_rgba = nullptr;
-    a.out_rad = nullptr;
     a.counters = stats ? p.d_counters : nullptr;
-    a.diag = nullptr;
     a.coop_lanes = a.scene.n_layouts ? 0 : (ctx->coop_lanes >= 0 ? ctx->coop_lanes : 1);
-    a.ext = 0;
     a.solo_lanes = p.last_solo = solo_lanes_of(ctx, a.scene, a.coop_lanes, 0);
-    a.sky_enabled = 1;
-    a.frame_count = 0;
-    a.accum = nullptr;
     a.walk = 2;
     a.block_waves = 1;
-    a.tile_order = nullptr;
-    a.tiles_x = 0;
-    a.split_n = a.heavy_tiles = a.heavy_fused = a.n_heavy_px = 0;
-    a.heavy_px = nullptr;
-    a.tile_mask = nullptr;
-    a.diag_lane = nullptr;
-    a.aux_stream = nullptr;
-    a.ev_fork = a.ev_join = nullptr;
-    a.coop_walk = 0;
-    a.coop_win = 64;
     a.any_hit = (flags & RT_QUERY_ANY) ? 1 : 0;
-    if (stats) {
-        RT_HIP_CHECK(hipMemsetAsync(p.d_counters, 0, sizeof(Counters), s));
-        RT_HIP_CHECK(hipEventRecord(p.ev0, s));
-    }
+    if (stats)
+        if (int rb = stats_begin(p, s)) return rb;
     RT_HIP_CHECK(launch_query(a, s));
-    if (stats) {
-        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        return collect_stats(ctx, p, n, stats, false);
-    }
-    return RT_OK;
+    if (stats) RT_HIP_CHECK(hipEventRecord(p.ev1, s));
+    return stats_end(p, n, stats);
 }
 
 static int query_staging(PerDevice& p, size_t bytes) {
@@ -1749,9 +1872,8 @@ int rt_query_rays_device(rt_ctx* ctx, const rt_ray* d_rays, size_t n_rays, uint3
     PerDevice& p = ctx->dev[0];
     RT_HIP_CHECK(hipSetDevice(p.device));
     TraceArgs a;
-    a.cams[0] = CamF{};
     a.width = (int)n_rays; a.height = 1;
-    a.x0 = 0; a.y0 = 0; a.tw = (int)n_rays; a.th = 1;
+    a.tw = (int)n_rays; a.th = 1;
     a.band_h = 1;
     a.wave_tile = 3;                                     // 64 x 1: ray i is lane i % 64 of wave i / 64
     a.ray_in = reinterpret_cast<const float4*>(d_rays);
@@ -1801,7 +1923,6 @@ int rt_render_hits_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int 
     a.x0 = x0; a.y0 = y0; a.tw = tile_w; a.th = tile_h;
     a.band_h = tile_h;
     a.wave_tile = wave_tile_of(ctx, p);                  // the render's wave tiles: the same walks side by side
-    a.ray_in = nullptr;
     a.hit_out = reinterpret_cast<float4*>(d_hits);
     return run_query(ctx, p, a, (uint64_t)tile_w * (uint64_t)tile_h, flags, static_cast<hipStream_t>(stream), stats);
 }
@@ -1911,14 +2032,7 @@ static int denoise_device(const char* fn, bool history, rt_ctx* ctx, int width, 
     d.only_pass = ctx->denoise_pass < q.iterations ? ctx->denoise_pass : -1;
     if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
     RT_HIP_CHECK(history ? launch_denoise_history(d, static_cast<const float4*>(d_in), s) : launch_denoise(d, s));
-    if (ms) {
-        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        float t = 0.0f;
-        RT_HIP_CHECK(hipEventElapsedTime(&t, p.ev0, p.ev1));
-        *ms = (double)t;
-    }
-    return RT_OK;
+    return ms ? elapsed_ms(p, s, ms) : RT_OK;
 }
 
 int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radiance, const rt_hit* d_hits,
@@ -2020,14 +2134,7 @@ int rt_denoise_variance_device(rt_ctx* ctx, int width, int height, const void* d
     d.stage = ctx->variance_stage;
     if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
     RT_HIP_CHECK(launch_denoise_variance(d, s));
-    if (ms) {
-        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        float t = 0.0f;
-        RT_HIP_CHECK(hipEventElapsedTime(&t, p.ev0, p.ev1));
-        *ms = (double)t;
-    }
-    return RT_OK;
+    return ms ? elapsed_ms(p, s, ms) : RT_OK;
 }
 
 int rt_render_denoised(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
@@ -2190,14 +2297,7 @@ static int temporal_device(const char* fn, bool moments, rt_ctx* ctx, int width,
     RT_HIP_CHECK(moments ? launch_temporal_moments(t, static_cast<const float2*>(d_mom_prev),
                                                    static_cast<float2*>(d_mom_out), s)
                          : launch_temporal(t, s));
-    if (ms) {
-        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        float e = 0.0f;
-        RT_HIP_CHECK(hipEventElapsedTime(&e, p.ev0, p.ev1));
-        *ms = (double)e;
-    }
-    return RT_OK;
+    return ms ? elapsed_ms(p, s, ms) : RT_OK;
 }
 
 int rt_temporal_device(rt_ctx* ctx, int width, int height, const rt_camera_ubo* cam, const float* d_radiance,
@@ -2291,12 +2391,13 @@ static int render_temporal(const char* fn, int mode, rt_ctx* ctx, const rt_camer
     char* d_hist[2] = {base + o_hist, base + o_hist + up(px * 16)};
     rt_hit* d_hits[2] = {reinterpret_cast<rt_hit*>(base + o_hits), reinterpret_cast<rt_hit*>(base + o_hits + up(px * 32))};
     float* d_trad = reinterpret_cast<float*>(base + o_trad);
-    // the ordinary render of the frame, with a new sample per frame_count for this launch
-    const int new_sample = ctx->new_sample;
-    if (!(flags & RT_TEMPORAL_FIXED_SEED)) ctx->new_sample = 1;
-    rc = rt_render_tile_device(ctx, cam, width, height, max_bounces, 0, 0, width, height, nullptr, d_rad, p.stream,
-                               stats);
-    ctx->new_sample = new_sample;
+    // the ordinary render of the frame (rt_render_tile_device's launch of the whole frame; its checks
+    // are the ones passed above), with a new sample per frame_count for this launch
+    RenderLaunch l = frame_launch(cam, 1, width, height, max_bounces);
+    l.band_h = height; l.rows = height;
+    l.rad = d_rad;
+    l.new_sample = !(flags & RT_TEMPORAL_FIXED_SEED);
+    rc = render_on_stream(ctx, l, (uint64_t)px, p.stream, stats);
     if (rc) return rc;
     rc = rt_render_hits_device(ctx, cam, width, height, 0, 0, width, height, 0, d_hits[cur], p.stream, nullptr);
     if (rc) return rc;
@@ -2378,91 +2479,6 @@ int rt_band_rows(int height, int band_h, int band_stride, int band_off) {
     return rows;
 }
 
-// A band list on the device (rt_render_batch_device), uploaded once per
-// distinct list and kept for the context's lifetime (a launch in flight may
-// still read it); past kMaxBandLists the device is drained and they are
-// dropped.
-static constexpr size_t kMaxBandLists = 256;
-
-static int device_band_list(PerDevice& p, const std::vector<int>& bands, const int** out) {
-    for (const auto& l : p.band_lists)
-        if (l.bands == bands) { *out = l.d; return RT_OK; }
-    if (p.band_lists.size() >= kMaxBandLists) {
-        RT_HIP_CHECK(hipDeviceSynchronize());
-        for (auto& l : p.band_lists) (void)hipFree(l.d);
-        p.band_lists.clear();
-    }
-    int* d = nullptr;
-    RT_HIP_CHECK(hipMalloc(&d, std::max<size_t>(1, bands.size()) * sizeof(int)));
-    const hipError_t e = hipMemcpy(d, bands.data(), bands.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        RT_HIP_CHECK(e);
-    }
-    p.band_lists.push_back(PerDevice::BandList{bands, d});
-    *out = d;
-    return RT_OK;
-}
-
-// One launch over the same rows of n_frames frames (camera cams[f] each):
-// the band_h-row bands b with b mod band_stride == band_off, or, with
-// `bands`, the listed bands; rows per frame = rows.  Outputs hold the frames
-// one after another (n_frames x rows x width).
-static int render_rows_on(const rt_ctx* ctx, PerDevice& p, const rt_camera_ubo* cams, int n_frames, int width,
-                          int height, int max_bounces, int band_h, int band_stride, int band_off,
-                          const std::vector<int>* bands, int rows, uchar4* d_rgba, float* d_rad, hipStream_t s,
-                          bool count, int list_stride = 0, int x0 = 0, int y0 = 0, int tile_w = 0,
-                          bool row_offsets = false) {
-    TraceArgs a;
-    a.scene = p.scene;
-    for (int f = 0; f < n_frames; ++f) a.cams[f] = cam_from_ubo(cams + f);
-    a.n_frames = n_frames;
-    a.width = width; a.height = height; a.max_bounces = max_bounces;
-    a.x0 = x0; a.y0 = y0; a.tw = tile_w > 0 ? tile_w : width; a.th = rows;
-    a.band_h = band_h; a.band_stride = band_stride; a.band_off = band_off;
-    a.band_list = nullptr;
-    a.list_stride = bands ? list_stride : 0;
-    if (bands)
-        if (int rb = device_band_list(p, *bands, &a.band_list)) return rb;
-    // row_offsets: the list ends with each frame's first output row
-    a.row_off = (bands && row_offsets) ? a.band_list + (size_t)n_frames * list_stride : nullptr;
-    a.out_rgba = d_rgba;
-    a.out_rad = d_rad;
-    a.counters = count ? p.d_counters : nullptr;
-    if (int rs = set_schedule(ctx, p, a, cams, bands)) return rs;
-    if (count) {
-        RT_HIP_CHECK(hipMemsetAsync(p.d_counters, 0, sizeof(Counters), s));
-        RT_HIP_CHECK(hipEventRecord(p.ev0, s));   // the timing events exist for stats only
-    }
-    if (int rl = launch(ctx, p, a, s)) return rl;
-    if (int ro = learn_order(ctx, p, a, s)) return ro;
-    if (count) RT_HIP_CHECK(hipEventRecord(p.ev1, s));
-    return RT_OK;
-}
-
-static int render_bands_on(const rt_ctx* ctx, PerDevice& p, const rt_camera_ubo* cam, int width, int height,
-                           int max_bounces, int band_h, int band_stride, int band_off, int rows,
-                           uchar4* d_rgba, float* d_rad, hipStream_t s, bool count) {
-    return render_rows_on(ctx, p, cam, 1, width, height, max_bounces, band_h, band_stride, band_off, nullptr, rows,
-                          d_rgba, d_rad, s, count);
-}
-
-static int collect_stats(const rt_ctx* ctx, PerDevice& p, uint64_t pixels, rt_stats* stats, bool accumulate) {
-    (void)ctx;
-    Counters c;
-    RT_HIP_CHECK(hipMemcpy(&c, p.d_counters, sizeof c, hipMemcpyDeviceToHost));
-    float ms = 0.f;
-    RT_HIP_CHECK(hipEventElapsedTime(&ms, p.ev0, p.ev1));
-    if (!accumulate) std::memset(stats, 0, sizeof *stats);
-    stats->pixels += pixels;
-    stats->segments += c.segments;
-    stats->node_visits += c.node_visits;
-    stats->tri_tests += c.tri_tests;
-    stats->mat_reads += c.mat_reads;
-    if (ms > stats->ms) stats->ms = ms;
-    return RT_OK;
-}
-
 int rt_render_bands_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
                            int band_h, int band_stride, int band_off,
                            void* d_out_rgba, void* d_out_radiance, void* stream, rt_stats* stats) {
@@ -2473,21 +2489,13 @@ int rt_render_bands_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int
         set_error("rt_render_bands_device: bad bands (band_h %d, stride %d, offset %d)", band_h, band_stride, band_off);
         return RT_ERR_INVALID_ARG;
     }
-    if (rows == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
-    PerDevice& p = ctx->dev[0];
-    RT_HIP_CHECK(hipSetDevice(p.device));
-    hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the null stream
-    rc = render_bands_on(ctx, p, cam, width, height, max_bounces, band_h, band_stride, band_off, rows,
-                         static_cast<uchar4*>(d_out_rgba), static_cast<float*>(d_out_radiance), s, stats != nullptr);
-    if (rc) return rc;
-    if (stats) {
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        return collect_stats(ctx, p, (uint64_t)rows * width, stats, false);
-    }
-    return RT_OK;
+    if (rows == 0) return nothing_to_trace(stats);
+    RenderLaunch l = frame_launch(cam, 1, width, height, max_bounces);
+    l.band_h = band_h; l.band_stride = band_stride; l.band_off = band_off;
+    l.rows = rows;
+    l.rgba = static_cast<uchar4*>(d_out_rgba);
+    l.rad = static_cast<float*>(d_out_radiance);
+    return render_on_stream(ctx, l, (uint64_t)rows * width, stream, stats);
 }
 
 int rt_band_list_rows(int height, int band_h, const int32_t* bands, int n_bands) {
@@ -2504,12 +2512,8 @@ int rt_band_list_rows(int height, int band_h, const int32_t* bands, int n_bands)
 int rt_render_batch_device(rt_ctx* ctx, const rt_camera_ubo* cams, int n_frames, int width, int height,
                            int max_bounces, int band_h, const int32_t* bands, int n_bands,
                            void* d_out_rgba, void* d_out_radiance, void* stream, rt_stats* stats) {
-    int rc = check_render_args(ctx, cams, width, height, max_bounces, "rt_render_batch_device");
-    if (rc) return rc;
-    if (n_frames < 1 || n_frames > kMaxBatch) {
-        set_error("rt_render_batch_device: n_frames must be in [1, %d], got %d", kMaxBatch, n_frames);
-        return RT_ERR_INVALID_ARG;
-    }
+    if (int rc = check_batch_args(ctx, cams, n_frames, width, height, max_bounces, "rt_render_batch_device"))
+        return rc;
     int rows;
     std::vector<int> list;
     if (bands) {
@@ -2524,22 +2528,14 @@ int rt_render_batch_device(rt_ctx* ctx, const rt_camera_ubo* cams, int n_frames,
         band_h = height;                     // the whole frame
         rows = height;
     }
-    if (rows == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
-    PerDevice& p = ctx->dev[0];
-    RT_HIP_CHECK(hipSetDevice(p.device));
-    hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the null stream
-    rc = render_rows_on(ctx, p, cams, n_frames, width, height, max_bounces, band_h, 1, 0, bands ? &list : nullptr,
-                        rows, static_cast<uchar4*>(d_out_rgba), static_cast<float*>(d_out_radiance), s,
-                        stats != nullptr);
-    if (rc) return rc;
-    if (stats) {
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        return collect_stats(ctx, p, (uint64_t)rows * width * n_frames, stats, false);
-    }
-    return RT_OK;
+    if (rows == 0) return nothing_to_trace(stats);
+    RenderLaunch l = frame_launch(cams, n_frames, width, height, max_bounces);
+    l.band_h = band_h;
+    l.bands = bands ? &list : nullptr;
+    l.rows = rows;
+    l.rgba = static_cast<uchar4*>(d_out_rgba);
+    l.rad = static_cast<float*>(d_out_radiance);
+    return render_on_stream(ctx, l, (uint64_t)rows * width * n_frames, stream, stats);
 }
 
 // ------------------------------------------------------------------ samples --
@@ -2575,39 +2571,6 @@ static int check_samples_args(const char* fn, rt_ctx* ctx, const rt_camera_ubo* 
     return RT_OK;
 }
 
-// One trace launch of a samples call: samples first .. first + n_frames - 1 of
-// `cam` as the frames of a whole-frame batch launch, their linear colours one
-// frame after another at d_lin.  The launcher, the learned order and the
-// schedule are rt_render_batch_device's.  The order's key sees the camera
-// with frame_count 0: the sample index moves the jitter, not the tiles' cost,
-// so a call's chunks and later calls share one learned order.
-static int samples_trace(const rt_ctx* ctx, PerDevice& p, const rt_camera_ubo* cam, int first, int n_frames,
-                         int width, int height, int max_bounces, float* d_lin, hipStream_t s, bool count) {
-    TraceArgs a;
-    a.scene = p.scene;
-    rt_camera_ubo cams[kMaxBatch];
-    for (int f = 0; f < n_frames; ++f) {
-        cams[f] = *cam;
-        cams[f].frame_count = 0;
-        a.cams[f] = cam_from_ubo(cam);
-    }
-    a.n_frames = n_frames;
-    a.width = width; a.height = height; a.max_bounces = max_bounces;
-    a.x0 = 0; a.y0 = 0; a.tw = width; a.th = height;
-    a.band_h = height; a.band_stride = 1; a.band_off = 0;
-    a.band_list = nullptr;
-    a.list_stride = 0;
-    a.out_rgba = nullptr;
-    a.out_rad = nullptr;
-    a.sample_step = 1;
-    a.out_lin = d_lin;
-    a.counters = count ? p.d_counters : nullptr;
-    if (int rs = set_schedule(ctx, p, a, cams)) return rs;
-    a.frame_count = first;
-    if (int rl = launch(ctx, p, a, s)) return rl;
-    return learn_order(ctx, p, a, s);
-}
-
 int rt_render_samples_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
                              int n_samples, void* d_workspace, size_t workspace_bytes, float* d_sum,
                              void* d_out_rgba, float* d_out_radiance, void* stream, rt_stats* stats) {
@@ -2641,17 +2604,23 @@ int rt_render_samples_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, i
     RT_HIP_CHECK(hipSetDevice(p.device));
     hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the null stream
     const int first = cam->frame_count;
-    if (stats) {
-        // the counting kernels add to the counters: zeroed once, they end as the call's totals
-        RT_HIP_CHECK(hipMemsetAsync(p.d_counters, 0, sizeof(Counters), s));
-        RT_HIP_CHECK(hipEventRecord(p.ev0, s));
-    }
+    // One trace launch per chunk: a whole-frame batch launch whose frames are
+    // consecutive samples of `cam`, their linear colours one frame after
+    // another in the workspace.  The launcher, the learned order and the
+    // schedule are rt_render_batch_device's.
+    RenderLaunch l = frame_launch(cam, 1, width, height, max_bounces);
+    l.band_h = height; l.rows = height;
+    l.lin = static_cast<float*>(d_workspace);
+    l.count = stats != nullptr;
+    // the counting kernels add to the counters: zeroed once, they end as the call's totals
+    if (stats)
+        if (int rb = stats_begin(p, s)) return rb;
     for (int done = 0; done < n_samples;) {
         const int c = std::min(std::min(ctx->sample_frames, frames_ws), n_samples - done);
+        l.n_frames = c;
+        l.first_sample = first + done;
         if (ctx->samples_stage != 1)
-            if (int rt = samples_trace(ctx, p, cam, first + done, c, width, height, max_bounces,
-                                       static_cast<float*>(d_workspace), s, stats != nullptr))
-                return rt;
+            if (int rt = enqueue_render(ctx, p, l, s)) return rt;
         done += c;
         if (ctx->samples_stage == 0) continue;
         SamplesArgs r;
@@ -2667,12 +2636,8 @@ int rt_render_samples_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, i
         r.form = ctx->samples_kernel;
         RT_HIP_CHECK(launch_samples_resolve(r, s));
     }
-    if (stats) {
-        RT_HIP_CHECK(hipEventRecord(p.ev1, s));
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        return collect_stats(ctx, p, (uint64_t)px * (uint64_t)n_samples, stats, false);
-    }
-    return RT_OK;
+    if (stats) RT_HIP_CHECK(hipEventRecord(p.ev1, s));
+    return stats_end(p, (uint64_t)px * (uint64_t)n_samples, stats);
 }
 
 int rt_render_samples(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces, int n_samples,
@@ -2729,34 +2694,20 @@ int rt_render_samples(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int heig
 int rt_render_batch_rect_device(rt_ctx* ctx, const rt_camera_ubo* cams, int n_frames, int width, int height,
                                 int max_bounces, int x0, int y0, int tile_w, int tile_h,
                                 void* d_out_rgba, void* d_out_radiance, void* stream, rt_stats* stats) {
-    int rc = check_render_args(ctx, cams, width, height, max_bounces, "rt_render_batch_rect_device");
-    if (rc) return rc;
-    if (n_frames < 1 || n_frames > kMaxBatch) {
-        set_error("rt_render_batch_rect_device: n_frames must be in [1, %d], got %d", kMaxBatch, n_frames);
-        return RT_ERR_INVALID_ARG;
-    }
+    if (int rc = check_batch_args(ctx, cams, n_frames, width, height, max_bounces, "rt_render_batch_rect_device"))
+        return rc;
     if (x0 < 0 || y0 < 0 || tile_w < 0 || tile_h < 0 || x0 + tile_w > width || y0 + tile_h > height) {
         set_error("rt_render_batch_rect_device: rectangle (%d, %d) %d x %d outside the %d x %d frame", x0, y0, tile_w,
                   tile_h, width, height);
         return RT_ERR_INVALID_ARG;
     }
-    if (tile_w == 0 || tile_h == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
-    PerDevice& p = ctx->dev[0];
-    RT_HIP_CHECK(hipSetDevice(p.device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // the rectangle's rows are one band of tile_h rows starting at y0
-    rc = render_rows_on(ctx, p, cams, n_frames, width, height, max_bounces, tile_h, 1, 0, nullptr, tile_h,
-                        static_cast<uchar4*>(d_out_rgba), static_cast<float*>(d_out_radiance), s, stats != nullptr, 0,
-                        x0, y0, tile_w);
-    if (rc) return rc;
-    if (stats) {
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        return collect_stats(ctx, p, (uint64_t)tile_w * tile_h * n_frames, stats, false);
-    }
-    return RT_OK;
+    if (tile_w == 0 || tile_h == 0) return nothing_to_trace(stats);
+    RenderLaunch l = frame_launch(cams, n_frames, width, height, max_bounces);
+    l.x0 = x0; l.tw = tile_w;
+    l.y0 = y0; l.band_h = tile_h; l.rows = tile_h;   // the rectangle's rows: one band of tile_h rows starting at y0
+    l.rgba = static_cast<uchar4*>(d_out_rgba);
+    l.rad = static_cast<float*>(d_out_radiance);
+    return render_on_stream(ctx, l, (uint64_t)tile_w * tile_h * n_frames, stream, stats);
 }
 
 int rt_render_batch_runs_device(rt_ctx* ctx, const rt_camera_ubo* cams, int n_frames, int width, int height,
@@ -2779,10 +2730,7 @@ int rt_render_batch_runs_device(rt_ctx* ctx, const rt_camera_ubo* cams, int n_fr
         }
         n_per = std::max(n_per, band_hi[f] - band_lo[f]);
     }
-    if (n_per == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
+    if (n_per == 0) return nothing_to_trace(stats);
     // one band list per frame, -1 padded to the longest run, then each
     // frame's first output row (its rows follow the previous frame's)
     std::vector<int> list((size_t)n_frames * n_per + n_frames, -1);
@@ -2795,18 +2743,13 @@ int rt_render_batch_runs_device(rt_ctx* ctx, const rt_camera_ubo* cams, int n_fr
         row += rows_f;
         pixels += (uint64_t)rows_f * (uint64_t)width;
     }
-    PerDevice& p = ctx->dev[0];
-    RT_HIP_CHECK(hipSetDevice(p.device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = render_rows_on(ctx, p, cams, n_frames, width, height, max_bounces, band_h, 1, 0, &list, n_per * band_h,
-                        static_cast<uchar4*>(d_out_rgba), static_cast<float*>(d_out_radiance), s, stats != nullptr,
-                        n_per, 0, 0, 0, true);
-    if (rc) return rc;
-    if (stats) {
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        return collect_stats(ctx, p, pixels, stats, false);
-    }
-    return RT_OK;
+    RenderLaunch l = frame_launch(cams, n_frames, width, height, max_bounces);
+    l.band_h = band_h;
+    l.bands = &list; l.list_stride = n_per; l.row_offsets = true;
+    l.rows = n_per * band_h;
+    l.rgba = static_cast<uchar4*>(d_out_rgba);
+    l.rad = static_cast<float*>(d_out_radiance);
+    return render_on_stream(ctx, l, pixels, stream, stats);
 }
 
 int rt_band_lists_rows(int height, int band_h, const int32_t* bands, int n_frames, int n_per) {
@@ -2825,12 +2768,8 @@ int rt_band_lists_rows(int height, int band_h, const int32_t* bands, int n_frame
 int rt_render_batch_lists_device(rt_ctx* ctx, const rt_camera_ubo* cams, int n_frames, int width, int height,
                                  int max_bounces, int band_h, const int32_t* bands, int n_per,
                                  void* d_out_rgba, void* d_out_radiance, void* stream, rt_stats* stats) {
-    int rc = check_render_args(ctx, cams, width, height, max_bounces, "rt_render_batch_lists_device");
-    if (rc) return rc;
-    if (n_frames < 1 || n_frames > kMaxBatch) {
-        set_error("rt_render_batch_lists_device: n_frames must be in [1, %d], got %d", kMaxBatch, n_frames);
-        return RT_ERR_INVALID_ARG;
-    }
+    if (int rc = check_batch_args(ctx, cams, n_frames, width, height, max_bounces, "rt_render_batch_lists_device"))
+        return rc;
     const int rows = rt_band_lists_rows(height, band_h, bands, n_frames, n_per);
     if (rows < 0) {
         set_error("rt_render_batch_lists_device: bad band lists (height %d, band_h %d, %d per frame: band_h must "
@@ -2845,23 +2784,15 @@ int rt_render_batch_lists_device(rt_ctx* ctx, const rt_camera_ubo* cams, int n_f
         while (k < n_per && l[k] >= 0) ++k;
         pixels += (uint64_t)rt_band_list_rows(height, band_h, l, k) * (uint64_t)width;
     }
-    if (rows == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
-    PerDevice& p = ctx->dev[0];
-    RT_HIP_CHECK(hipSetDevice(p.device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    // (rows >= band_h: rt_band_lists_rows takes no empty lists, so there is always something to trace)
     const std::vector<int> list(bands, bands + (size_t)n_frames * n_per);
-    rc = render_rows_on(ctx, p, cams, n_frames, width, height, max_bounces, band_h, 1, 0, &list, rows,
-                        static_cast<uchar4*>(d_out_rgba), static_cast<float*>(d_out_radiance), s,
-                        stats != nullptr, n_per);
-    if (rc) return rc;
-    if (stats) {
-        RT_HIP_CHECK(hipEventSynchronize(p.ev1));
-        return collect_stats(ctx, p, pixels, stats, false);
-    }
-    return RT_OK;
+    RenderLaunch l = frame_launch(cams, n_frames, width, height, max_bounces);
+    l.band_h = band_h;
+    l.bands = &list; l.list_stride = n_per;
+    l.rows = rows;
+    l.rgba = static_cast<uchar4*>(d_out_rgba);
+    l.rad = static_cast<float*>(d_out_radiance);
+    return render_on_stream(ctx, l, pixels, stream, stats);
 }
 
 int rt_render(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
@@ -2876,14 +2807,19 @@ int rt_render(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int 
     const int bh = nd == 1 ? height : 16;
     std::vector<int> rows(nd);
     for (int k = 0; k < nd; ++k) rows[k] = rt_band_rows(height, bh, nd, k);
+    RenderLaunch l = frame_launch(cam, 1, width, height, max_bounces);
+    l.band_h = bh; l.band_stride = nd;
+    l.count = stats != nullptr;
     for (int k = 0; k < nd; ++k) {
         if (rows[k] == 0) continue;
         PerDevice& p = ctx->dev[k];
         RT_HIP_CHECK(hipSetDevice(p.device));
         rc = ensure_out(p, (size_t)width * rows[k], out_radiance != nullptr);
         if (rc) return rc;
-        rc = render_bands_on(ctx, p, cam, width, height, max_bounces, bh, nd, k, rows[k], p.d_rgba,
-                             out_radiance ? p.d_rad : nullptr, p.stream, stats != nullptr);
+        l.band_off = k; l.rows = rows[k];
+        l.rgba = p.d_rgba;
+        l.rad = out_radiance ? p.d_rad : nullptr;
+        rc = enqueue_render(ctx, p, l, p.stream);
         if (rc) return rc;
     }
     if (stats) std::memset(stats, 0, sizeof *stats);
@@ -2915,7 +2851,7 @@ int rt_render(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int 
             }
         }
         if (stats) {
-            rc = collect_stats(ctx, p, px, stats, true);
+            rc = collect_stats(p, px, stats, true);
             if (rc) return rc;
         }
     }
@@ -2980,10 +2916,12 @@ int rt_render_async(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height
             const int prev = (int)((t - 1) % (uint64_t)S);
             if (p.slot_ticket[prev] == t - 1) RT_HIP_CHECK(hipStreamWaitEvent(ts, p.traced[prev], 0));
         }
-        ctx->in_async = S;
-        rc = render_bands_on(ctx, p, cam, width, height, max_bounces, bh, nd, k, rows, p.d_ring[slot], nullptr, ts,
-                             false);
-        ctx->in_async = 0;
+        RenderLaunch l = frame_launch(cam, 1, width, height, max_bounces);
+        l.band_h = bh; l.band_stride = nd; l.band_off = k;
+        l.rows = rows;
+        l.rgba = p.d_ring[slot];
+        l.in_flight = S;
+        rc = enqueue_render(ctx, p, l, ts);
         if (rc) return rc;
         RT_HIP_CHECK(hipEventRecord(p.traced[slot], ts));
         // Copies run in ticket order on the one copy stream, whatever order the

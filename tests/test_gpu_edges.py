@@ -1,6 +1,6 @@
 """GPU parity at ragged frame, band and batch shapes, on every launch path.
 
-The hand-written part of trace_simple and of render_rows_on / plan_order maps
+The hand-written part of trace_simple and of enqueue_render / plan_order maps
 a lane to a pixel, a local row to a frame row, a workgroup to a tile and a
 frame to an output row.  The other GPU suites run that mapping almost only
 where nothing is partial; here every entry point runs at widths and heights
