@@ -127,7 +127,14 @@ __device__ __forceinline__ void primary_ray_seeded(const TraceArgs& a, int f, in
 // on closest_t (ind) and t_enter; the box is hit iff ind && te < closest_t.
 typedef float f2 __attribute__((ext_vector_type(2)));
 
+__device__ __forceinline__ void slab_t(float4 A, float4 B, V3 o, V3 inv, float& te, float& tx);
 __device__ __forceinline__ void slab(float4 A, float4 B, V3 o, V3 inv, float& te, bool& ind) {
+    float tx;
+    slab_t(A, B, o, inv, te, tx);
+    ind = tx > te && tx > kTMin;
+}
+// t_enter and t_exit of the slab test (ind is t_exit > t_enter && t_exit > T_MIN).
+__device__ __forceinline__ void slab_t(float4 A, float4 B, V3 o, V3 inv, float& te, float& tx) {
     // x and y in packed FP32 (v_pk_add_f32 / v_pk_mul_f32: two IEEE binary32
     // operations per lane per instruction, each rounded exactly as the scalar one).
     const f2 oxy = {o.x, o.y}, ixy = {inv.x, inv.y};
@@ -136,8 +143,7 @@ __device__ __forceinline__ void slab(float4 A, float4 B, V3 o, V3 inv, float& te
     const float t0x = t0.x, t1x = t1.x, t0y = t0.y, t1y = t1.y;
     const float t0z = (A.z - o.z) * inv.z, t1z = (B.z - o.z) * inv.z;
     te = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z));
-    const float tx = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
-    ind = tx > te && tx > kTMin;
+    tx = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
 }
 
 // hit_triangle (:105-129) up to its final "t < closest_t" compare: returns
@@ -1002,23 +1008,35 @@ __device__ __forceinline__ void solo_walk(const float4* __restrict__ walk, int L
                                           float& lim, unsigned long long& c_node, unsigned long long& c_tri,
                                           unsigned long long& d_iters) {
     const bool me = (int)(threadIdx.x & 63) == L;
+    const uint64_t lbit = 1ull << L;
     unsigned cn = 0, ct = 0, steps = 0;
+    // The step's wave-uniform flags are 32-bit integers (0 / 1): lane L's
+    // predicate is read from its bit of the compares' masks, which are
+    // combined as 64-bit integers, and the next offset and the leaf flag come
+    // by scalar selects.  (As bools the flags were built as 64-bit lane masks,
+    // sent through a v_cndmask / v_cmp pair for the ballot and combined with
+    // exec: 24 scalar instructions a step.)
+    unsigned lf = sl ? 1u : 0u;
     for (;;) {
         const u32x8 R = srec(walk, sb);
         u32x8 T;
-        if (sl) T = srec(walk, sb + 32u);                        // a leaf's triangle: the slot after its box
+        if (lf) T = srec(walk, sb + 32u);                            // a leaf's triangle: the slot after its box
         const uint32_t aw = R[3], bw = R[7];
-        float te;
-        bool ind;
-        slab(make_float4(__uint_as_float(R[0]), __uint_as_float(R[1]), __uint_as_float(R[2]), 0.f),
-             make_float4(__uint_as_float(R[4]), __uint_as_float(R[5]), __uint_as_float(R[6]), 0.f), o, inv, te, ind);
-        const bool hb = ((__ballot(ind && accel_enter_lim(te, lim, aw)) >> L) & 1ull) != 0ull;
-        const unsigned tb = sb + (sl ? 64u : 32u);
-        sb = (hb || sl) ? tb : (aw << 5);
-        const bool nl = (hb && !sl) ? (int)bw < 0 : (int)aw < 0;
-        if (COUNT && hb && !sl) cn += 2;
+        float te, tx;
+        slab_t(make_float4(__uint_as_float(R[0]), __uint_as_float(R[1]), __uint_as_float(R[2]), 0.f),
+               make_float4(__uint_as_float(R[4]), __uint_as_float(R[5]), __uint_as_float(R[6]), 0.f), o, inv, te, tx);
+        // slab's ind && accel_enter_lim(te, lim, aw), one compare per mask
+        const uint64_t forced = (aw & kForce) != 0u ? ~0ull : 0ull;
+        const uint64_t m = __builtin_amdgcn_ballot_w64(tx > te) & __builtin_amdgcn_ballot_w64(tx > kTMin) &
+                           (__builtin_amdgcn_ballot_w64(te <= lim) | forced);
+        const unsigned hb = (unsigned)(m >> L) & 1u;
+        const unsigned tb = sb + 32u + (lf << 5);
+        sb = (hb | lf) ? tb : (aw << 5);
+        const unsigned first = hb & ~lf;                             // into an internal record's first child
+        const uint32_t nw = first ? bw : aw;                         // the next record's L bit is its sign
+        if (COUNT && first) cn += 2;
         if (DIAG) ++steps;
-        if (hb && sl) {                                              // hit_triangle (:196-200)
+        if (hb & lf) {                                               // hit_triangle (:196-200)
             if (COUNT) ++ct;
             float t;
             const bool tv = tri_test(make_float4(__uint_as_float(bw), __uint_as_float(T[0]), __uint_as_float(T[1]), 0.f),
@@ -1026,17 +1044,17 @@ __device__ __forceinline__ void solo_walk(const float4* __restrict__ walk, int L
                                      make_float4(__uint_as_float(T[5]), __uint_as_float(T[6]), __uint_as_float(T[7]), 0.f),
                                      o, d, t) &&
                             accel_take(t, (int)(aw & kTri), closest, hit);
-            if (((__ballot(tv) >> L) & 1ull) != 0ull && me) {
+            if ((__builtin_amdgcn_ballot_w64(tv) & lbit) != 0ull && me) {
                 closest = t;
                 hit = (int)(aw & kTri);
                 incons = t < te;
                 lim = accel_lim(t);
             }
         }
-        sl = nl;
+        lf = nw >> 31;
         if (!(sb < se)) break;
         // RT_QUERY_ANY: the first hit closest mode would keep as consistent ends the walk
-        if (QRY && any_hit && ((__ballot(hit >= 0 && !incons) >> L) & 1ull) != 0ull) break;
+        if (QRY && any_hit && (__builtin_amdgcn_ballot_w64(hit >= 0 && !incons) & lbit) != 0ull) break;
     }
     if (me) {
         if (COUNT) {
@@ -1394,8 +1412,75 @@ void trace_simple(TraceArgs a) {
             // L bit), and the slot index is recovered after the loop.
             constexpr bool BYTES = ACC && !HALF && !WIDE && !PAD && WALK == 2;
             unsigned nb = (unsigned)n << 5;
-            const unsigned lend_b = (unsigned)lend << 5;
-            while (walking) {
+            // (a lane that does not walk at all has an empty range, so that
+            // nb < lend_b alone says whether a lane's walk is open)
+            const unsigned lend_b = walk0 ? (unsigned)lend << 5 : 0u;
+            if (BYTES) {
+                // The format-0 lockstep loop.  A lane's state lives in VGPR
+                // integers: nb, and lw, whose sign bit says that the record at
+                // nb is a leaf (it is the link word the step selected).  No lane
+                // mask is carried round the loop but w, the lanes still walking,
+                // which is one compare of nb after the step; the loop itself is
+                // wave-uniform with one exit: the count of w against the lanes
+                // the loop leaves to solo_walk or the cooperative tail.  (As
+                // loop-carried bools, nleaf and walking cost an andn2 / and / or
+                // triple each at every join: 25 scalar instructions a step.)
+                uint32_t lw = nleaf ? 0x80000000u : 0u;
+                const int keep = SOLO ? a.solo_lanes : ((FEAT & kFeatCoopTail) ? coop_lanes : 0);
+                bool w = walking;
+                if (__ballot(w) != 0ull) {
+                    do {
+                        if (w) {
+                            if (DIAG) ++d_iters;
+                            float te;
+                            bool ind;
+                            slab(A, B, o, inv, te, ind);
+                            const uint32_t aw = __float_as_uint(A.w), bw = __float_as_uint(B.w);
+                            const bool lf = (int)lw < 0;
+                            const bool hb = ind && accel_enter_lim(te, lim, aw);
+                            // a leaf's next record is two slots on, hit or not; an internal
+                            // record's left child is the next slot, its skip aw << 5
+                            const unsigned tb = nb + (lf ? 64u : 32u);       // known before the slab test ends
+                            nb = (hb || lf) ? tb : (aw << 5);
+                            // the next record's link word: L(first) is bit 31 of word 7,
+                            // L(skip) / L(next) bit 31 of word 3.  It and v0.x are taken
+                            // before the next record's loads overwrite A and B, so nothing
+                            // waits for those loads at the bottom of the step.  (A leaf's
+                            // word is its own aw: the triangle index is read from lw.)
+                            const bool hl = hb && lf;
+                            lw = (hb != hl) ? bw : aw;
+                            float v0x;                                       // a leaf's v0.x
+                            asm volatile("v_mov_b32 %0, %2" : "=v"(v0x), "+v"(lw) : "v"(B.w));
+                            if (COUNT && hb && !lf) c_node += 2;
+                            A = wbuf_b(wrs, nb, 0);                          // slot end is padding
+                            B = wbuf_b(wrs, nb, 16);
+                            if (hl) {                                        // hit_triangle (:196-200)
+                                if (COUNT) ++c_tri;
+                                float t;
+                                const int tri = (int)(lw & kTri);
+                                if (tri_test(make_float4(v0x, Q0.x, Q0.y, 0.f), make_float4(Q0.z, Q0.w, Q1.x, 0.f),
+                                             make_float4(Q1.y, Q1.z, Q1.w, 0.f), o, d, t) &&
+                                    accel_take(t, tri, closest, hit)) {
+                                    closest = t;
+                                    hit = tri;
+                                    incons = t < te;
+                                    lim = accel_lim(t);
+                                }
+                            }
+                            if ((int)lw < 0 && nb < lend_b) {
+                                Q0 = wbuf_b(wrs, nb, 32);
+                                Q1 = wbuf_b(wrs, nb, 48);
+                            }
+                        }
+                        w = nb < lend_b;
+                        // RT_QUERY_ANY: the first hit closest mode would keep as consistent ends the walk
+                        if (QRY) w = w && !(a.any_hit && hit >= 0 && !incons);
+                    } while (__popcll(__ballot(w)) > keep);
+                }
+                walking = w;
+                nleaf = (int)lw < 0;
+            }
+            while (!BYTES && walking) {
                 if (DIAG) ++d_iters;
                 if (WIDE) {
                     walking = wide_step<COUNT>(wrs, fr + (size_t)wave * (kWideStackK * 64 * 6 / 16), o, d, inv, closest,
@@ -1463,10 +1548,6 @@ void trace_simple(TraceArgs a) {
                         const int m_hit = -(int)hb, m_leaf = -(int)nleaf;
                         const int n_int = (n_hit & m_hit) | ((int)(aw & kIdx) & ~m_hit);
                         nxt = (n_leaf & m_leaf) | (n_int & ~m_leaf);
-                    } else if (BYTES) {
-                        const unsigned tb = nb + (nleaf ? 64u : 32u);        // known before the slab test ends
-                        nb = (hb || nleaf) ? tb : (aw << 5);
-                        nxt = 0;                                             // (the slot: nb >> 5)
                     } else {
                         const int t = n + 1 + (int)nleaf;                    // known before the slab test ends
                         nxt = (hb || nleaf) ? t : (int)(aw & kIdx);
@@ -1477,13 +1558,8 @@ void trace_simple(TraceArgs a) {
                                         : ((((hb && !nleaf) ? bw : (aw >> 31)) & 1u) != 0u);
                     const float v0x = B.w;                                   // a leaf's v0.x
                     if (COUNT && hb && !nleaf) c_node += 2;
-                    if (BYTES) {
-                        A = wbuf_b(wrs, nb, 0);                              // slot end is padding
-                        B = wbuf_b(wrs, nb, 16);
-                    } else {
-                        A = wbuf(wrs, nxt, 0);                               // slot end is padding
-                        B = wbuf(wrs, nxt, 16);
-                    }
+                    A = wbuf(wrs, nxt, 0);                                   // slot end is padding
+                    B = wbuf(wrs, nxt, 16);
                     if (hb && nleaf) {                                       // hit_triangle (:196-200)
                         if (COUNT) ++c_tri;
                         float t;
@@ -1498,17 +1574,12 @@ void trace_simple(TraceArgs a) {
                             }
                         }
                     }
-                    const bool inb = BYTES ? nb < lend_b : nxt < (ACC ? lend : wend);
+                    const bool inb = nxt < (ACC ? lend : wend);
                     if (nl && inb) {
-                        if (BYTES) {
-                            Q0 = wbuf_b(wrs, nb, 32);
-                            Q1 = wbuf_b(wrs, nb, 48);
-                        } else {
-                            Q0 = wbuf(wrs, nxt, 32);
-                            Q1 = wbuf(wrs, nxt, 48);
-                        }
+                        Q0 = wbuf(wrs, nxt, 32);
+                        Q1 = wbuf(wrs, nxt, 48);
                     }
-                    if (!BYTES) n = nxt;
+                    n = nxt;
                     nleaf = nl;
                     walking = inb;
                     // RT_QUERY_ANY: the first hit closest mode would keep as consistent ends the walk
@@ -1516,10 +1587,6 @@ void trace_simple(TraceArgs a) {
                 }
                 if (WALK == 0 || HALF) walking = n < (ACC ? lend : wend);
                 if ((FEAT & kFeatCoopTail) && __popcll(__ballot(walking)) <= coop_lanes) break;
-                // kFeatSolo: the last solo_lanes walks leave the loop by its own
-                // condition (a break here cost the loop a second exit and ~25
-                // scalar instructions per step)
-                if (SOLO) walking = walking && __popcll(__ballot(walking)) > a.solo_lanes;
             }
             if (SOLO) {
                 // Every lane is here.  The walks still open (inside their layout,
