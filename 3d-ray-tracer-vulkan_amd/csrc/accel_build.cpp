@@ -371,8 +371,9 @@ uint16_t half_bits_down(float x) {
 
 int accel_build(const void* vertices, size_t vertex_bytes, const void* materials, size_t material_bytes,
                 const void* bvh_nodes, size_t bvh_bytes, int n_layouts, int n_threads, AccelHost* out,
-                std::string* err, int format, int64_t cap_slots) {
+                std::string* err, int format, int64_t cap_slots, bool refit_tables) {
     *out = AccelHost{};
+    if (format != 0) refit_tables = false;
     if (format < 0 || format > 2) {
         *err = "accel: format must be 0, 1 or 2";
         return -1;
@@ -441,6 +442,10 @@ int accel_build(const void* vertices, size_t vertex_bytes, const void* materials
             for (size_t j = s; j < i; ++j)
                 if (!dup[order[j]] && same(occ[order[i]], occ[order[j]])) {
                     dup[order[i]] = 1;
+                    if (refit_tables) {
+                        const Occ &d = occ[order[i]], &k = occ[order[j]];
+                        out->dup_pairs.insert(out->dup_pairs.end(), {d.tri, (int32_t)d.node, k.tri, (int32_t)k.node});
+                    }
                     break;
                 }
         s = e;
@@ -454,6 +459,7 @@ int accel_build(const void* vertices, size_t vertex_bytes, const void* materials
             p.c[q] = 0.5f * (p.lo[q] + p.hi[q]);
         }
         p.tri = occ[i].tri;
+        if (refit_tables) out->prim_leaf.push_back((int32_t)occ[i].node);
         {
             const unsigned char* v = vb + (size_t)p.tri * 48;
             float x[9];
@@ -522,6 +528,26 @@ int accel_build(const void* vertices, size_t vertex_bytes, const void* materials
     const size_t total = (size_t)slots * (size_t)n_layouts;
     out->rec.assign((size_t)W * total + 16, 0u);
     std::vector<uint8_t> leaf_at(total + 1, 0);
+    const size_t nn = B.nodes.size();
+    if (refit_tables) {
+        out->node_child.resize(2 * nn);
+        out->node_height.assign(nn, 0);
+        out->node_slot.assign(nn * (size_t)n_layouts, 0u);
+        out->prim_tri.resize(m);
+        out->prim_node.resize(m);
+        // a child's id is above its parent's: heights settle from the last node to the first
+        for (size_t c = nn; c-- > 0;) {
+            const BNode& nd = B.nodes[c];
+            out->node_child[2 * c] = nd.left;
+            out->node_child[2 * c + 1] = nd.right;
+            if (nd.prim >= 0) {
+                out->prim_tri[nd.prim] = B.prims[nd.prim].tri;
+                out->prim_node[nd.prim] = (int32_t)c;
+            } else {
+                out->node_height[c] = 1 + std::max(out->node_height[nd.left], out->node_height[nd.right]);
+            }
+        }
+    }
     auto emit = [&](int o) {
         const size_t base = (size_t)o * (size_t)slots;
         struct Item { int node; size_t pos; };
@@ -532,6 +558,7 @@ int accel_build(const void* vertices, size_t vertex_bytes, const void* materials
             st.pop_back();
             const BNode& nd = B.nodes[it.node];
             uint32_t* w = &out->rec[(size_t)W * it.pos];
+            if (refit_tables) out->node_slot[(size_t)o * nn + (size_t)it.node] = (uint32_t)it.pos;
             if (nd.prim >= 0 || format == 0) {
                 for (int q = 0; q < 3; ++q) {
                     put_f(&w[q], nd.lo[q]);
@@ -604,13 +631,202 @@ int accel_build(const void* vertices, size_t vertex_bytes, const void* materials
 
 int accel_build_fit(const void* vertices, size_t vertex_bytes, const void* materials, size_t material_bytes,
                     const void* bvh_nodes, size_t bvh_bytes, int n_layouts, AccelHost* out, std::string* err,
-                    int format, int64_t cap_slots) {
+                    int format, int64_t cap_slots, bool refit_tables) {
     int rc = accel_build(vertices, vertex_bytes, materials, material_bytes, bvh_nodes, bvh_bytes, n_layouts, 0, out,
-                         err, format, cap_slots);
+                         err, format, cap_slots, refit_tables);
     if (rc == kAccelTooBig && n_layouts == 8)
         rc = accel_build(vertices, vertex_bytes, materials, material_bytes, bvh_nodes, bvh_bytes, 1, 0, out, err,
-                         format, cap_slots);
+                         format, cap_slots, refit_tables);
     return rc;
+}
+
+
+float accel_union_lo(float a, float b) { return std::min(a, b); }
+float accel_union_hi(float a, float b) { return std::max(a, b); }
+
+int accel_refit_records(uint32_t* words, int n_layouts, int slots, const void* vertices, size_t vertex_bytes,
+                        const void* bvh_nodes, size_t bvh_bytes, std::string* err) {
+    const size_t n_nodes = bvh_bytes / 48, n_tris = vertex_bytes / 48;
+    const unsigned char* nb = static_cast<const unsigned char*>(bvh_nodes);
+    const unsigned char* vb = static_cast<const unsigned char*>(vertices);
+    constexpr uint32_t kIdx = kAccelForce - 1;         // a skip or a triangle index
+    // the reference leaf that names a flattened triangle
+    std::vector<int32_t> leaf_of(n_tris, -1);
+    for (size_t k = 0; k < n_nodes; ++k) {
+        int32_t data, count;
+        std::memcpy(&data, nb + k * 48 + 32, 4);
+        std::memcpy(&count, nb + k * 48 + 36, 4);
+        if (count >= 0) continue;
+        const int64_t tri = -((int64_t)data + 1);
+        if (tri < 0 || (size_t)tri >= n_tris) {
+            *err = "leaf " + std::to_string(k) + " names triangle " + std::to_string(tri) + " outside the buffers";
+            return -1;
+        }
+        if (leaf_of[tri] >= 0) {
+            *err = "leaves " + std::to_string(leaf_of[tri]) + " and " + std::to_string(k) + " both name triangle " +
+                   std::to_string(tri);
+            return -1;
+        }
+        leaf_of[tri] = (int32_t)k;
+    }
+    if (slots == 0) return 0;
+    const size_t S = (size_t)slots, total = S * (size_t)n_layouts;
+    // 1. the slots that start a node, layout by layout in preorder; every link checked before it is followed
+    std::vector<uint32_t> starts;
+    starts.reserve(total);
+    std::vector<uint8_t> is_start(n_layouts > 1 ? S : 0, 0);      // of layout 0, for step 4
+    std::vector<size_t> first(n_layouts + 1, 0);
+    for (int o = 0; o < n_layouts; ++o) {
+        const size_t base = (size_t)o * S, end = base + S;
+        first[o] = starts.size();
+        for (size_t s = base; s < end;) {
+            const uint32_t w3 = words[8 * s + 3];
+            starts.push_back((uint32_t)s);
+            if (o == 0 && n_layouts > 1) is_start[s] = 1;
+            if ((w3 >> 30) & 1u) {
+                const uint32_t tri = w3 & kIdx;
+                if (s + 2 > end || tri >= n_tris || leaf_of[tri] < 0) {
+                    *err = "slot " + std::to_string(s) + ": a leaf past its layout, or of a triangle no reference leaf names";
+                    return -1;
+                }
+                s += 2;
+            } else {
+                const size_t skip = w3 & kIdx;
+                if (skip < s + 5 || skip > end) {          // two children of at least two slots each
+                    *err = "slot " + std::to_string(s) + ": an internal record whose skip leaves its layout";
+                    return -1;
+                }
+                s += 1;
+            }
+        }
+        if (first[o] + (size_t)(2 * ((S + 1) / 3) - 1) != starts.size()) {
+            *err = "layout " + std::to_string(o) + " is not a tree of one-triangle leaves";
+            return -1;
+        }
+    }
+    first[n_layouts] = starts.size();
+    // A triangle a reference leaf names but the records do not hold was dropped at the build as a
+    // byte-identical copy of one they hold (accel_build step 1; the materials take no part here): its
+    // new vertex record and leaf box must still be some held triangle's, or the records cannot stand
+    // for the moved scene.
+    {
+        std::vector<uint8_t> held(n_tris, 0);
+        for (size_t i = first[0]; i < first[1]; ++i) {
+            const uint32_t w3 = words[8 * (size_t)starts[i] + 3];
+            if ((w3 >> 30) & 1u) held[w3 & kIdx] = 1;
+        }
+        const auto hash = [&](size_t tri) {
+            uint64_t h = fnv(vb + tri * 48, 48, 1469598103934665603ull);
+            h = fnv(nb + (size_t)leaf_of[tri] * 48, 12, h);
+            return fnv(nb + (size_t)leaf_of[tri] * 48 + 16, 12, h);
+        };
+        std::vector<std::pair<uint64_t, uint32_t>> keys;
+        bool dropped = false;
+        for (size_t t = 0; t < n_tris; ++t) dropped = dropped || (leaf_of[t] >= 0 && !held[t]);
+        if (dropped) {
+            for (size_t t = 0; t < n_tris; ++t)
+                if (held[t]) keys.push_back({hash(t), (uint32_t)t});
+            std::sort(keys.begin(), keys.end());
+        }
+        for (size_t t = 0; dropped && t < n_tris; ++t) {
+            if (leaf_of[t] < 0 || held[t]) continue;
+            const uint64_t h = hash(t);
+            bool found = false;
+            for (auto it = std::lower_bound(keys.begin(), keys.end(), std::make_pair(h, (uint32_t)0));
+                 it != keys.end() && it->first == h && !found; ++it) {
+                const unsigned char *a = nb + (size_t)leaf_of[t] * 48, *b = nb + (size_t)leaf_of[it->second] * 48;
+                found = std::memcmp(vb + t * 48, vb + (size_t)it->second * 48, 48) == 0 && std::memcmp(a, b, 12) == 0 &&
+                        std::memcmp(a + 16, b + 16, 12) == 0;
+            }
+            if (!found) {
+                *err = "triangle " + std::to_string(t) + " was dropped from the records as a byte-identical copy and " +
+                       "is no longer one";
+                return -1;
+            }
+        }
+    }
+    const auto leaf = [&](size_t s) { return (words[8 * s + 3] >> 30) & 1u; };
+    const auto span = [&](size_t s) { return leaf(s) ? (size_t)2 : (size_t)(words[8 * s + 3] & kIdx) - s; };
+    // 2. the least triangle of every subtree: it tells a node's two children apart in any layout
+    std::vector<uint32_t> min_tri(total, 0u);
+    for (size_t i = starts.size(); i-- > 0;) {
+        const size_t s = starts[i];
+        if (leaf(s)) {
+            min_tri[s] = words[8 * s + 3] & kIdx;
+            continue;
+        }
+        const size_t a = s + 1, b = a + span(a);
+        if (b >= (words[8 * s + 3] & kIdx)) {
+            *err = "slot " + std::to_string(s) + ": the first child fills the subtree";
+            return -1;
+        }
+        min_tri[s] = std::min(min_tri[a], min_tri[b]);
+    }
+    const auto write_leaf = [&](size_t s) {
+        uint32_t* w = words + 8 * s;
+        const uint32_t tri = w[3] & kIdx;
+        const unsigned char* r = nb + (size_t)leaf_of[tri] * 48;
+        std::memcpy(&w[0], r, 12);
+        std::memcpy(&w[4], r + 16, 12);
+        float x[9];
+        for (int j = 0; j < 3; ++j) std::memcpy(&x[3 * j], vb + (size_t)tri * 48 + 16 * j, 12);
+        // e1 = v1 - v0, e2 = v2 - v0, as accel_build writes them
+        const float e1[3] = {x[3] - x[0], x[4] - x[1], x[5] - x[2]};
+        const float e2[3] = {x[6] - x[0], x[7] - x[1], x[8] - x[2]};
+        w[3] = (w[3] & ~kAccelForce) | (accel_class(e1, e2) >= kAccelClassMin ? kAccelForce : 0u);
+        for (int j = 0; j < 3; ++j) {
+            put_f(&w[7 + j], x[j]);
+            put_f(&w[10 + j], e1[j]);
+            put_f(&w[13 + j], e2[j]);
+        }
+    };
+    // 3. layout 0, children before parents: its first child is the lower-centroid one
+    for (size_t i = first[1]; i-- > 0;) {
+        const size_t s = starts[i];
+        if (leaf(s)) {
+            write_leaf(s);
+            continue;
+        }
+        uint32_t* w = words + 8 * s;
+        const uint32_t* a = words + 8 * (s + 1);
+        const uint32_t* b = words + 8 * (s + 1 + span(s + 1));
+        for (int q = 0; q < 3; ++q) {
+            float al, bl, ah, bh;
+            std::memcpy(&al, &a[q], 4);
+            std::memcpy(&bl, &b[q], 4);
+            std::memcpy(&ah, &a[4 + q], 4);
+            std::memcpy(&bh, &b[4 + q], 4);
+            put_f(&w[q], accel_union_lo(al, bl));
+            put_f(&w[4 + q], accel_union_hi(ah, bh));
+        }
+        w[3] = (w[3] & ~kAccelForce) | ((a[3] | b[3]) & kAccelForce);
+    }
+    // 4. the other layouts, parents before children: every node takes its layout-0 twin's box and bit
+    std::vector<uint32_t> twin(n_layouts > 1 ? total : 0, 0u);
+    for (int o = 1; o < n_layouts; ++o) {
+        twin[(size_t)o * S] = 0u;
+        for (size_t i = first[o]; i < first[o + 1]; ++i) {
+            const size_t s = starts[i], c = twin[s];
+            if (c >= S || !is_start[c] || leaf(s) != leaf(c) || min_tri[s] != min_tri[c] || span(s) != span(c)) {
+                *err = "layout " + std::to_string(o) + " slot " + std::to_string(s) + " has no twin in layout 0";
+                return -1;
+            }
+            if (leaf(s)) {
+                write_leaf(s);
+                continue;
+            }
+            uint32_t* w = words + 8 * s;
+            const uint32_t* wc = words + 8 * c;
+            std::memcpy(&w[0], &wc[0], 12);
+            std::memcpy(&w[4], &wc[4], 12);
+            w[3] = (w[3] & ~kAccelForce) | (wc[3] & kAccelForce);
+            const size_t sa = s + 1, sb = sa + span(sa), ca = c + 1, cb = ca + span(ca);
+            const bool same = min_tri[sa] == min_tri[ca];
+            twin[sa] = (uint32_t)(same ? ca : cb);
+            twin[sb] = (uint32_t)(same ? cb : ca);
+        }
+    }
+    return 0;
 }
 
 }  // namespace rtamd

@@ -84,6 +84,18 @@ struct AccelHost {
     int max_class = 0;              // the largest shape class (accel_class) of the primitives
     int n_thin = 0;                 // primitives of class >= kAccelClassMin
     float relax_max = 0.0f;         // accel_relax(max_class): format 1's margin for every internal node
+    // What a refit of the records needs (option "refit"), filled
+    // only when accel_build is asked for them (format 0 only), empty otherwise.
+    // Canonical node c is the builder's node id, 0 = the root, 2 n_prims - 1 in
+    // all; a leaf's children are -1.
+    std::vector<int32_t> node_child;    // 2 per canonical node: the lower-centroid child, then the other
+    std::vector<int32_t> node_height;   // per canonical node: 0 at a leaf, else 1 + the larger of its children's
+    std::vector<uint32_t> node_slot;    // n_layouts per canonical node: [o * nodes + c] = c's slot in layout o,
+                                        //   counted from the start of the records
+    std::vector<int32_t> prim_tri;      // per kept primitive: its flattened triangle,
+    std::vector<int32_t> prim_leaf;     //   the reference leaf node that holds its box,
+    std::vector<int32_t> prim_node;     //   and its canonical leaf node
+    std::vector<int32_t> dup_pairs;     // 4 per dropped duplicate: its triangle and reference leaf, its keeper's
 };
 
 // The shape class of a triangle, floor(-log2 sin(angle at v0)) in 0..31
@@ -130,7 +142,7 @@ float wide_decode(float origin, int q, int e);
 // format: 0 or 1 (above).
 int accel_build(const void* vertices, size_t vertex_bytes, const void* materials, size_t material_bytes,
                 const void* bvh_nodes, size_t bvh_bytes, int n_layouts, int n_threads, AccelHost* out,
-                std::string* err, int format = 0, int64_t cap_slots = 0);
+                std::string* err, int format = 0, int64_t cap_slots = 0, bool refit_tables = false);
 
 // accel_build with the capacity fallback: n_layouts 8 that do not fit become
 // 1 layout (out->n_layouts says which).  Returns 0, kAccelTooBig when one
@@ -138,7 +150,23 @@ int accel_build(const void* vertices, size_t vertex_bytes, const void* materials
 // tree, option accel 0, whose records reach ~45 M triangles), or -1.
 int accel_build_fit(const void* vertices, size_t vertex_bytes, const void* materials, size_t material_bytes,
                     const void* bvh_nodes, size_t bvh_bytes, int n_layouts, AccelHost* out, std::string* err,
-                    int format = 0, int64_t cap_slots = 0);
+                    int format = 0, int64_t cap_slots = 0, bool refit_tables = false);
+
+// Refits format-0 records in place (rt_accel_refit_records, rtamd.h): every
+// leaf slot pair takes the box of the reference leaf that names its triangle,
+// v0 / e1 / e2 and its force bit from the moved vertices; every internal slot
+// the union of its children's boxes (accel_union_lo / _hi: the Builder's
+// std::min / std::max with the lower-centroid child, layout 0's first, as the
+// first operand) and the OR of their force bits.  Nothing else changes.
+// `slots` per layout; the buffers have passed build_host_scene's validation
+// and bvh_bytes covers the root's subtree.  Returns 0, or -1 with *err set:
+// two leaves naming one triangle, words that are no such records, or a
+// triangle that step 1 of the build dropped as a byte-identical copy and that
+// no longer matches any triangle the records hold.
+float accel_union_lo(float a, float b);   // std::min(a, b): a on a tie, signed zeros included
+float accel_union_hi(float a, float b);   // std::max(a, b)
+int accel_refit_records(uint32_t* words, int n_layouts, int slots, const void* vertices, size_t vertex_bytes,
+                        const void* bvh_nodes, size_t bvh_bytes, std::string* err);
 
 // Half-precision bits of the largest half <= x (-inf below -65504), and of the
 // smallest half >= x: the outward rounding of format 1's internal boxes.

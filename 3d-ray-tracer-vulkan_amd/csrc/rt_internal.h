@@ -380,4 +380,30 @@ struct SamplesArgs {
 };
 hipError_t launch_samples_resolve(const SamplesArgs& r, hipStream_t stream);
 
+// rt_refit.hip: the scene's records recomputed in place from moved vertices
+// (rtamd.h rt_update_geometry).  The tables are device arrays
+// written at an upload with option refit 1; the two staging arrays are what a
+// call copies in.
+struct RefitTables {
+    const float4* st_verts = nullptr;   // staging: the raw vertex records, 3 float4 per flattened triangle
+    const float*  st_boxes = nullptr;   // staging: 6 floats per reference node (min.xyz, max.xyz)
+    int           n_ref = 0;            // reference nodes of the root's subtree (HostScene::end)
+    int           n_tris = 0;           // flattened triangles
+    const int*    ref_info = nullptr;   // per reference node: a leaf's triangle, or -(right child + 1)
+    const int*    ref_slot = nullptr;   // per reference node: its slot in the reference's walk records
+    // the accel tree (format 0): AccelHost's tables
+    int           n_layouts = 0, n_canon = 0, n_prims = 0;
+    const int*    prim = nullptr;       // 3 per kept primitive: triangle, reference leaf, canonical node
+    const int*    child = nullptr;      // 2 per canonical node
+    const uint32_t* slot = nullptr;     // n_layouts per canonical node: [o * n_canon + c]
+    const int*    by_height = nullptr;  // the internal canonical nodes grouped by height, lowest first
+    float4*       canon = nullptr;      // 2 per canonical node: (min.xyz, force bit), (max.xyz, 0)
+};
+struct RefitArgs {
+    DevScene    scene;
+    RefitTables t;
+};
+// Enqueues the three stages on `stream`; level_first: n_levels + 1 offsets into by_height (host memory).
+hipError_t launch_refit(const RefitArgs& r, const int* level_first, int n_levels, hipStream_t stream);
+
 }  // namespace rtamd

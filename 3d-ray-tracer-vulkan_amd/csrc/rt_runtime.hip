@@ -344,6 +344,11 @@ struct PerDevice {
     char*        d_samples = nullptr;
     size_t       samples_cap = 0;    // bytes
     int          samples_held = 0, samples_w = 0, samples_h = 0;
+    // option refit: rt_update_geometry's staging and tables, one allocation of refit_bytes (rt_internal.h
+    // RefitTables; refit's pointers lie inside it), null when the scene holds none
+    char*        d_refit = nullptr;
+    size_t       refit_bytes = 0;
+    RefitTables  refit;
 };
 
 static constexpr size_t kMaxOrders = 16;
@@ -495,6 +500,15 @@ struct rt_ctx {
     int  heavy_tiles = -1;         // heavy_first: the this-many most expensive tiles are traced one pixel
                                    //   per wave, walked cooperatively, in a separate launch
                                    //   (-1 = automatic: the tiles that outlast the bulk, learn_order)
+    int  refit = 0;                // at the next upload: keep what rt_update_geometry needs
+    // The host side of those tables: the uploaded buffers' sizes, every node's 24 bytes outside its boxes
+    // (offsets 12-15 and 28-47), the duplicates the accel build dropped (AccelHost::dup_pairs) and where
+    // each height's nodes start in RefitTables::by_height.  refit_held: the current scene has them.
+    bool refit_held = false;
+    size_t refit_vertex_bytes = 0, refit_bvh_bytes = 0;
+    std::vector<uint8_t> refit_links;
+    std::vector<int32_t> refit_dups;
+    std::vector<int> refit_level_first;
     uint64_t scene_gen = 0;        // bumped by every scene upload (invalidates learned tile orders)
     int  hw_queues = 4;            // GPU_MAX_HW_QUEUES seen at rt_create (HIP's default 4); frames in
                                    //   flight on more streams than queues - 2 share queues and serialise
@@ -512,6 +526,10 @@ static void free_scene(PerDevice& p) {
     if (p.scene.node_slot) (void)hipFree(p.scene.node_slot);
     if (p.scene.pairs) (void)hipFree(p.scene.pairs);
     if (p.scene.norms) (void)hipFree(p.scene.norms);   // mats lives in the same allocation
+    if (p.d_refit) (void)hipFree(p.d_refit);
+    p.d_refit = nullptr;
+    p.refit_bytes = 0;
+    p.refit = RefitTables{};
     p.scene = DevScene{};
 }
 
@@ -1418,13 +1436,79 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
         std::string msg;
         const int rc = accel_build_fit(vertices, vertex_bytes, materials, material_bytes, bvh_nodes,
                                        (size_t)hs.end * RT_NODE_RECORD_BYTES, ctx->accel, &ah, &msg,
-                                       ctx->accel_wide ? 2 : ctx->accel_half ? 1 : 0, accel_cap_slots());
+                                       ctx->accel_wide ? 2 : ctx->accel_half ? 1 : 0, accel_cap_slots(),
+                                       ctx->refit != 0);
         if (rc != 0 && rc != kAccelTooBig) {
             free_host_scene(&hs);
             set_error("rt_upload_scene: %s", msg.c_str());
             return RT_ERR_BAD_SCENE;
         }
         acc = rc == 0;
+    }
+    // Option refit: what rt_update_geometry needs, laid out once as the bytes every device
+    // gets behind its staging buffers.  The half and wide record formats hold none.
+    ctx->refit_held = false;
+    const bool keep = ctx->refit && !(acc && ah.format != 0);
+    std::vector<uint8_t> rtab;                 // the tables, sections 16-B aligned
+    size_t o_info = 0, o_slot = 0, o_prim = 0, o_child = 0, o_lslot = 0, o_height = 0, o_canon = 0;
+    const size_t st_bytes = ((size_t)hs.n_tris * 48 + (size_t)hs.n_nodes * 24 + 15) / 16 * 16;
+    if (keep) {
+        const auto section = [&rtab](size_t bytes) {
+            const size_t at = rtab.size();
+            rtab.resize(at + (bytes + 15) / 16 * 16, 0);
+            return at;
+        };
+        o_info = section(4 * n2);
+        o_slot = section(4 * n2);
+        for (size_t i = 0; i < n2; ++i) {
+            uint32_t fl, v;
+            std::memcpy(&fl, &hs.nodes[2 * i + 1].w, 4);
+            if (fl & 2u) std::memcpy(&v, &hs.leafs[3 * i].w, 4);                 // the triangle
+            else {
+                std::memcpy(&v, &hs.pairs[4 * i + 3].x, 4);                      // the right child
+                v = (uint32_t)(-(int32_t)((v & 0x7FFFFFFFu) + 1));
+            }
+            std::memcpy(&rtab[o_info + 4 * i], &v, 4);
+            std::memcpy(&rtab[o_slot + 4 * i], &slot[i], 4);
+        }
+        ctx->refit_level_first.assign(1, 0);
+        if (acc && ah.slots > 0) {
+            const size_t m = ah.prim_tri.size(), nc = ah.node_height.size();
+            o_prim = section(12 * m);
+            for (size_t k = 0; k < m; ++k) {
+                const int32_t rec[3] = {ah.prim_tri[k], ah.prim_leaf[k], ah.prim_node[k]};
+                std::memcpy(&rtab[o_prim + 12 * k], rec, 12);
+            }
+            o_child = section(8 * nc);
+            std::memcpy(&rtab[o_child], ah.node_child.data(), 8 * nc);
+            o_lslot = section(4 * nc * (size_t)ah.n_layouts);
+            std::memcpy(&rtab[o_lslot], ah.node_slot.data(), 4 * nc * (size_t)ah.n_layouts);
+            // the internal nodes by height, lowest first (a counting sort), and where each height starts
+            int top = 0;
+            for (size_t c = 0; c < nc; ++c) top = std::max(top, ah.node_height[c]);
+            std::vector<int> first(top + 2, 0);
+            for (size_t c = 0; c < nc; ++c)
+                if (ah.node_height[c] > 0) ++first[ah.node_height[c] + 1];
+            for (int h = 1; h <= top + 1; ++h) first[h] += first[h - 1];
+            o_height = section(4 * (nc - m));
+            std::vector<int> at(first.begin(), first.end());
+            for (size_t c = 0; c < nc; ++c)
+                if (ah.node_height[c] > 0) {
+                    const int32_t id = (int32_t)c;
+                    std::memcpy(&rtab[o_height + 4 * (size_t)at[ah.node_height[c]]++], &id, 4);
+                }
+            ctx->refit_level_first.assign(first.begin() + 1, first.end());       // heights 1 .. top, then the end
+            o_canon = section(32 * nc);
+        }
+        const unsigned char* nbytes = static_cast<const unsigned char*>(bvh_nodes);
+        ctx->refit_links.resize(24 * (size_t)hs.n_nodes);
+        for (size_t i = 0; i < (size_t)hs.n_nodes; ++i) {
+            std::memcpy(&ctx->refit_links[24 * i], nbytes + 48 * i + 12, 4);
+            std::memcpy(&ctx->refit_links[24 * i + 4], nbytes + 48 * i + 28, 20);
+        }
+        ctx->refit_dups = acc ? ah.dup_pairs : std::vector<int32_t>();
+        ctx->refit_vertex_bytes = vertex_bytes;
+        ctx->refit_bvh_bytes = bvh_bytes;
     }
     ctx->has_scene = false;
     for (PerDevice& p : ctx->dev) {
@@ -1502,6 +1586,30 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
         if (e == hipSuccess && hs.n_tris)
             e = hipMemcpy2D(s.mats, kShadeStride * sizeof(float4), hs.mats, sizeof(float4), sizeof(float4),
                             (size_t)hs.n_tris, hipMemcpyHostToDevice);
+        if (e == hipSuccess && keep) {
+            p.refit_bytes = st_bytes + rtab.size();
+            e = hipMalloc(&p.d_refit, p.refit_bytes ? p.refit_bytes : 16);
+            if (e == hipSuccess && !rtab.empty())
+                e = hipMemcpy(p.d_refit + st_bytes, rtab.data(), rtab.size(), hipMemcpyHostToDevice);
+            RefitTables& t = p.refit;
+            char* tb = p.d_refit + st_bytes;
+            t.st_verts = reinterpret_cast<const float4*>(p.d_refit);
+            t.st_boxes = reinterpret_cast<const float*>(p.d_refit + (size_t)hs.n_tris * 48);
+            t.n_ref = hs.end;
+            t.n_tris = hs.n_tris;
+            t.ref_info = reinterpret_cast<const int*>(tb + o_info);
+            t.ref_slot = reinterpret_cast<const int*>(tb + o_slot);
+            if (acc && ah.slots > 0) {
+                t.n_layouts = ah.n_layouts;
+                t.n_canon = (int)ah.node_height.size();
+                t.n_prims = (int)ah.prim_tri.size();
+                t.prim = reinterpret_cast<const int*>(tb + o_prim);
+                t.child = reinterpret_cast<const int*>(tb + o_child);
+                t.slot = reinterpret_cast<const uint32_t*>(tb + o_lslot);
+                t.by_height = reinterpret_cast<const int*>(tb + o_height);
+                t.canon = reinterpret_cast<float4*>(tb + o_canon);
+            }
+        }
         // the padding memsets ran on the null stream: complete before any
         // launch stream (non-blocking) reads the scene
         if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -1518,10 +1626,126 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
     ctx->n_tris = hs.n_tris;
     ctx->max_depth = hs.max_depth;
     ctx->has_scene = true;
+    ctx->refit_held = keep;
     ++ctx->scene_gen;
     for (PerDevice& p : ctx->dev) p.temporal_valid = false;   // rt_render_temporal starts a new sequence
     for (PerDevice& p : ctx->dev) p.samples_held = 0;         // and rt_render_samples a new sum
     free_host_scene(&hs);
+    return RT_OK;
+}
+
+int rt_update_geometry(rt_ctx* ctx, const void* vertices, size_t vertex_bytes, const void* bvh_nodes, size_t bvh_bytes,
+                       double* ms) {
+    if (!ctx) { set_error("rt_update_geometry: null context"); return RT_ERR_INVALID_ARG; }
+    if (!ctx->has_scene) { set_error("rt_update_geometry: no scene uploaded"); return RT_ERR_NO_SCENE; }
+    if (!vertices || !bvh_nodes) { set_error("rt_update_geometry: null buffer"); return RT_ERR_INVALID_ARG; }
+    if (!ctx->refit_held) {
+        const DevScene& sc = ctx->dev[0].scene;
+        if (sc.half || sc.wide)
+            set_error("rt_update_geometry: the scene's accel records are in the %s format, which is not refitted "
+                      "(upload without accel_%s)", sc.half ? "half" : "wide", sc.half ? "half" : "wide");
+        else
+            set_error("rt_update_geometry: the scene holds no refit tables: set option refit to 1 before "
+                      "rt_upload_scene");
+        return RT_ERR_INVALID_ARG;
+    }
+    if (vertex_bytes != ctx->refit_vertex_bytes || bvh_bytes != ctx->refit_bvh_bytes) {
+        set_error("rt_update_geometry: %zu vertex bytes and %zu node bytes, the uploaded scene has %zu and %zu",
+                  vertex_bytes, bvh_bytes, ctx->refit_vertex_bytes, ctx->refit_bvh_bytes);
+        return RT_ERR_BAD_SCENE;
+    }
+    const size_t n_nodes = (size_t)ctx->n_nodes, n_tris = (size_t)ctx->n_tris;
+    const unsigned char* nb = static_cast<const unsigned char*>(bvh_nodes);
+    const unsigned char* vb = static_cast<const unsigned char*>(vertices);
+    for (size_t i = 0; i < n_nodes; ++i) {
+        const unsigned char* r = nb + 48 * i;
+        if (std::memcmp(r + 12, &ctx->refit_links[24 * i], 4) || std::memcmp(r + 28, &ctx->refit_links[24 * i + 4], 20)) {
+            set_error("rt_update_geometry: node %zu differs from the uploaded node outside its boxes", i);
+            return RT_ERR_BAD_SCENE;
+        }
+        for (int q = 0; q < 3; ++q)
+            if (!std::isfinite(f32_at(r, 4 * q)) || !std::isfinite(f32_at(r, 16 + 4 * q))) {
+                set_error("rt_update_geometry: node %zu has a box that is not finite", i);
+                return RT_ERR_BAD_SCENE;
+            }
+    }
+    for (size_t t = 0; t < n_tris; ++t)
+        for (int q = 0; q < 9; ++q)
+            if (!std::isfinite(f32_at(vb + 48 * t, 16 * (q / 3) + 4 * (q % 3)))) {
+                set_error("rt_update_geometry: triangle %zu has a vertex that is not finite", t);
+                return RT_ERR_BAD_SCENE;
+            }
+    // A triangle the accel build dropped as a byte-identical copy of another is not in the records: it must
+    // still be one (the materials did not change).
+    for (size_t k = 0; k + 3 < ctx->refit_dups.size(); k += 4) {
+        const int32_t* d = &ctx->refit_dups[k];
+        const unsigned char *dn = nb + 48 * (size_t)d[1], *kn = nb + 48 * (size_t)d[3];
+        if (std::memcmp(vb + 48 * (size_t)d[0], vb + 48 * (size_t)d[2], 48) || std::memcmp(dn, kn, 12) ||
+            std::memcmp(dn + 16, kn + 16, 12)) {
+            set_error("rt_update_geometry: triangle %d was dropped at upload as a byte-identical copy of triangle %d "
+                      "and no longer is one: upload the scene again", d[0], d[2]);
+            return RT_ERR_BAD_SCENE;
+        }
+    }
+    // the boxes alone, 24 B per node
+    std::vector<float> boxes(6 * n_nodes);
+    for (size_t i = 0; i < n_nodes; ++i) {
+        std::memcpy(&boxes[6 * i], nb + 48 * i, 12);
+        std::memcpy(&boxes[6 * i + 3], nb + 48 * i + 16, 12);
+    }
+    if (ms) *ms = 0.0;
+    for (PerDevice& p : ctx->dev) {
+        RT_HIP_CHECK(hipSetDevice(p.device));
+        RT_HIP_CHECK(hipDeviceSynchronize());            // frames in flight read the records rewritten below
+        p.temporal_valid = false;                        // rt_render_temporal starts a new sequence
+        p.samples_held = 0;                              // and rt_render_samples a new sum
+        if (n_nodes == 0) continue;                      // an empty scene stays empty
+        if (n_tris)
+            RT_HIP_CHECK(hipMemcpyAsync(const_cast<float4*>(p.refit.st_verts), vb, 48 * n_tris, hipMemcpyHostToDevice,
+                                        p.stream));
+        RT_HIP_CHECK(hipMemcpyAsync(const_cast<float*>(p.refit.st_boxes), boxes.data(), 24 * n_nodes,
+                                    hipMemcpyHostToDevice, p.stream));
+        RefitArgs r;
+        r.scene = p.scene;
+        r.t = p.refit;
+        const bool timed = ms && &p == &ctx->dev[0];
+        if (timed) RT_HIP_CHECK(hipEventRecord(p.ev0, p.stream));
+        RT_HIP_CHECK(launch_refit(r, ctx->refit_level_first.data(), (int)ctx->refit_level_first.size() - 1, p.stream));
+        if (timed) RT_HIP_CHECK(hipEventRecord(p.ev1, p.stream));
+        RT_HIP_CHECK(hipStreamSynchronize(p.stream));
+        if (timed) {
+            float t = 0.f;
+            RT_HIP_CHECK(hipEventElapsedTime(&t, p.ev0, p.ev1));
+            *ms = t;
+        }
+        std::memcpy(p.scene.root_box, boxes.data(), sizeof p.scene.root_box);
+    }
+    return RT_OK;
+}
+
+int rt_scene_copy_records(rt_ctx* ctx, int which, uint32_t* out_words, size_t cap_words, size_t* n_words) {
+    if (!ctx || !n_words) { set_error("rt_scene_copy_records: null argument"); return RT_ERR_INVALID_ARG; }
+    if (which < 0 || which > 5) { set_error("rt_scene_copy_records: which must be 0..5"); return RT_ERR_INVALID_ARG; }
+    if (!ctx->has_scene) { set_error("rt_scene_copy_records: no scene uploaded"); return RT_ERR_NO_SCENE; }
+    PerDevice& p = ctx->dev[0];
+    const DevScene& s = p.scene;
+    const bool accel = s.n_layouts > 0;
+    const void* src = nullptr;
+    size_t words = 0;
+    // the walk records carry 64 B of padding, as rt_accel_records' do
+    if (which == 0) { src = s.walk; words = (size_t)s.end2 * (s.half ? 4 : s.wide ? 16 : 8) + 16; }
+    else if (which == 1 && accel) { src = s.walk_ref; words = (size_t)s.end2_ref * 8 + 16; }
+    else if (which == 2) { src = s.norms; words = (size_t)s.n_tris * 4 * kShadeStride; }
+    else if (which == 3) { src = s.nodes; words = s.nodes ? (size_t)s.end * 8 : 0; }
+    else if (which == 4) { src = s.leafs; words = s.leafs ? (size_t)s.end * 12 : 0; }
+    else if (which == 5) { src = s.pairs; words = s.pairs ? (size_t)s.end * 16 : 0; }
+    if (!src) words = 0;
+    *n_words = words;
+    if (out_words && words) {
+        RT_HIP_CHECK(hipSetDevice(p.device));
+        RT_HIP_CHECK(hipDeviceSynchronize());
+        RT_HIP_CHECK(hipMemcpy(out_words, src, std::min(cap_words, words) * 4, hipMemcpyDeviceToHost));
+    }
     return RT_OK;
 }
 
@@ -3084,6 +3308,7 @@ static const Option kOptions[] = {
     one_of("accel", &rt_ctx::accel, 0, 1, 8),               //   rt_upload_scene
     one_of("accel_half", &rt_ctx::accel_half, 0, 1),
     one_of("accel_wide", &rt_ctx::accel_wide, 0, 1),
+    one_of("refit", &rt_ctx::refit, 0, 1),                  // and so does this one
     in_range("split_bounce", &rt_ctx::split_bounce, 0, 64),
     in_range("split_pixels", &rt_ctx::split_pixels, 0, 1 << 30),
     in_range("split_queues", &rt_ctx::split_queues, 1, kMaxSplitQueues),
@@ -3145,6 +3370,8 @@ int rt_get_option(rt_ctx* ctx, const char* name, int64_t* value) {
     else if (is("accel_wide_used")) *value = p ? p->scene.wide : 0;
     else if (is("accel_used")) *value = p ? p->scene.n_layouts : 0;
     else if (is("walk_bytes")) *value = p ? (int64_t)walk_bytes(*p) : 0;
+    else if (is("refit_used")) *value = ctx->refit_held ? 1 : 0;
+    else if (is("refit_bytes")) *value = p ? (int64_t)p->refit_bytes : 0;
     else if (is("leaf_align_used")) *value = p ? p->scene.padded : 0;
     else if (is("heavy_pixels_used")) *value = p ? p->last_heavy_px : 0;
     else if (is("heavy_tiles_used")) *value = p ? p->last_heavy : 0;
@@ -3327,6 +3554,36 @@ int rt_accel_records(const void* vertices, size_t vertex_bytes, const void* mate
         info[6] = ah.max_class; info[7] = ah.n_thin;
     }
     if (out_words) std::memcpy(out_words, ah.rec.data(), std::min(cap_words, ah.rec.size()) * sizeof(uint32_t));
+    return RT_OK;
+}
+
+int rt_accel_refit_records(uint32_t* words_inout, size_t n_words, int n_layouts, const void* vertices,
+                           size_t vertex_bytes, const void* bvh_nodes, size_t bvh_bytes) {
+    if (!words_inout || (n_layouts != 1 && n_layouts != 8) || n_words < 16 || (n_words - 16) % (8 * (size_t)n_layouts)) {
+        set_error("rt_accel_refit_records: need the words of rt_accel_records for n_layouts 1 or 8 "
+                  "(8 x n_layouts x slots + 16)");
+        return RT_ERR_INVALID_ARG;
+    }
+    const size_t slots = (n_words - 16) / (8 * (size_t)n_layouts);
+    if (slots > (size_t)INT32_MAX || (slots && slots % 3 != 2)) {
+        set_error("rt_accel_refit_records: %zu slots per layout are not a tree of one-triangle leaves", slots);
+        return RT_ERR_BAD_SCENE;
+    }
+    // the validation of an upload; the materials take no part (any buffer that covers the triangles)
+    const size_t n_tris = vertex_bytes < RT_VERTEX_RECORD_BYTES ? 0 : vertex_bytes / RT_VERTEX_RECORD_BYTES;
+    std::vector<float> mats(4 * std::max<size_t>(n_tris, 1), 0.f);
+    HostScene hs;
+    const char* err = nullptr;
+    int rc = build_host_scene(vertices, vertex_bytes, mats.data(), mats.size() * 4, bvh_nodes, bvh_bytes, &hs, &err);
+    if (rc != RT_OK) { set_error("rt_accel_refit_records: %s", err); return rc; }
+    const size_t reach = (size_t)hs.end * RT_NODE_RECORD_BYTES;    // the root's subtree only
+    free_host_scene(&hs);
+    std::string msg;
+    if (accel_refit_records(words_inout, n_layouts, (int)slots, vertices, n_tris * RT_VERTEX_RECORD_BYTES, bvh_nodes,
+                            reach, &msg) != 0) {
+        set_error("rt_accel_refit_records: %s", msg.c_str());
+        return RT_ERR_BAD_SCENE;
+    }
     return RT_OK;
 }
 

@@ -82,6 +82,24 @@ inline Box surround(const Box& a, const Box& b) {   // AABB.surroundingBox
     return r;
 }
 
+// Triangle.calculateBoundingBox (Triangle.java:61-71) of 9 doubles v0, v1, v2.
+inline Box tri_box(const double* v) {
+    const double eps = 0.0001;                 // Triangle.java:65
+    Box bx;
+    for (int k = 0; k < 3; ++k) {
+        bx.mn[k] = jmin(v[k], jmin(v[3 + k], v[6 + k]));
+        bx.mx[k] = jmax(v[k], jmax(v[3 + k], v[6 + k]));
+    }
+    // max = max.add(new Vec3(eps,0,0)) etc.: each add touches all
+    // three components (x + 0.0 turns -0.0 into +0.0).
+    for (int k = 0; k < 3; ++k) {
+        if (bx.mx[k] - bx.mn[k] < eps) {
+            for (int j = 0; j < 3; ++j) bx.mx[j] = bx.mx[j] + (j == k ? eps : 0.0);
+        }
+    }
+    return bx;
+}
+
 // Node / leaf counts for a range of n triangles (BVHBuilder.java:60-78).
 size_t nodes_for(size_t n) {
     if (n == 0) return 0;
@@ -222,21 +240,9 @@ int rt_build_scene_map(const double* tri_verts, const float* tri_mats, size_t n_
         b.tri_box.resize(n_tris);
         for (int a = 0; a < 3; ++a) b.key[a].resize(n_tris);
         b.order.resize(n_tris);
-        const double eps = 0.0001;                 // Triangle.java:65
         for (size_t t = 0; t < n_tris; ++t) {
-            const double* v = tri_verts + t * 9;
             Box& bx = b.tri_box[t];
-            for (int k = 0; k < 3; ++k) {
-                bx.mn[k] = jmin(v[k], jmin(v[3 + k], v[6 + k]));
-                bx.mx[k] = jmax(v[k], jmax(v[3 + k], v[6 + k]));
-            }
-            // max = max.add(new Vec3(eps,0,0)) etc.: each add touches all
-            // three components (x + 0.0 turns -0.0 into +0.0).
-            for (int k = 0; k < 3; ++k) {
-                if (bx.mx[k] - bx.mn[k] < eps) {
-                    for (int j = 0; j < 3; ++j) bx.mx[j] = bx.mx[j] + (j == k ? eps : 0.0);
-                }
-            }
+            bx = tri_box(tri_verts + t * 9);
             for (int a = 0; a < 3; ++a) b.key[a][t] = dkey((bx.mn[a] + bx.mx[a]) / 2.0);
             b.order[t] = (uint32_t)t;
         }
@@ -247,6 +253,64 @@ int rt_build_scene_map(const double* tri_verts, const float* tri_mats, size_t n_
     } catch (const std::exception& e) {
         set_error("rt_build_scene: %s", e.what());
         return RT_ERR_INVALID_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_refit_scene(const double* tri_verts, size_t n_tris, const uint32_t* source, size_t n_flat,
+                   float* out_vertices, void* nodes_inout, size_t n_nodes) {
+    if (n_flat == 0 && n_nodes == 0) return RT_OK;
+    if (!tri_verts || !source || !out_vertices || !nodes_inout) {
+        set_error("rt_refit_scene: null pointer");
+        return RT_ERR_INVALID_ARG;
+    }
+    unsigned char* nb = static_cast<unsigned char*>(nodes_inout);
+    try {
+        // the flattened triangles: Builder::write_leaf's casts
+        for (size_t f = 0; f < n_flat; ++f) {
+            if (source[f] >= n_tris) {
+                set_error("rt_refit_scene: flattened triangle %zu copies input triangle %u of %zu", f, source[f], n_tris);
+                return RT_ERR_BAD_SCENE;
+            }
+            const double* v = tri_verts + (size_t)source[f] * 9;
+            float* o = out_vertices + f * 12;
+            for (int k = 0; k < 3; ++k) {
+                o[4 * k + 0] = (float)v[3 * k + 0];
+                o[4 * k + 1] = (float)v[3 * k + 1];
+                o[4 * k + 2] = (float)v[3 * k + 2];
+                o[4 * k + 3] = 0.0f;
+            }
+        }
+        // the boxes in double, children (higher preorder indices) before parents, cast as write_node casts
+        std::vector<Box> box(n_nodes);
+        for (size_t k = n_nodes; k-- > 0;) {
+            unsigned char* r = nb + k * RT_NODE_RECORD_BYTES;
+            int32_t data, count;
+            std::memcpy(&data, r + 32, 4);
+            std::memcpy(&count, r + 36, 4);
+            if (count < 0) {
+                const int64_t f = -((int64_t)data + 1);
+                if (f < 0 || (size_t)f >= n_flat) {
+                    set_error("rt_refit_scene: leaf %zu names triangle %lld outside the %zu flattened", k, (long long)f,
+                              n_flat);
+                    return RT_ERR_BAD_SCENE;
+                }
+                box[k] = tri_box(tri_verts + (size_t)source[f] * 9);
+            } else {
+                if ((size_t)data <= k || (size_t)count <= k || (size_t)data >= n_nodes || (size_t)count >= n_nodes) {
+                    set_error("rt_refit_scene: node %zu: children %d and %d are not later nodes", k, data, count);
+                    return RT_ERR_BAD_SCENE;
+                }
+                box[k] = surround(box[data], box[count]);
+            }
+            const float mn[3] = {(float)box[k].mn[0], (float)box[k].mn[1], (float)box[k].mn[2]};
+            const float mx[3] = {(float)box[k].mx[0], (float)box[k].mx[1], (float)box[k].mx[2]};
+            std::memcpy(r, mn, 12);
+            std::memcpy(r + 16, mx, 12);
+        }
+    } catch (const std::bad_alloc&) {
+        set_error("rt_refit_scene: out of memory");
+        return RT_ERR_OOM;
     }
     return RT_OK;
 }

@@ -46,12 +46,12 @@ _want_queues()
 
 from ._lib import LIB_PATH, RtError, CameraUBO, DenoiseParams, Stats, TemporalParams, VarianceParams, lib  # noqa: E402
 from .scene import (BuiltCpuData, Camera, Mesh, ModelInstance, Scene, SceneBuilder,
-                    build_buffers, instance_of, triangles_of)
+                    build_buffers, instance_of, refit_buffers, triangles_of)
 from .engine import AtomicReference, FrameData, HipEngine, Renderer
 
 __all__ = [
     "LIB_PATH", "RtError", "CameraUBO", "DenoiseParams", "Stats", "TemporalParams", "VarianceParams", "lib",
     "BuiltCpuData", "Camera", "Mesh", "ModelInstance", "Scene", "SceneBuilder",
-    "build_buffers", "instance_of", "triangles_of",
+    "build_buffers", "instance_of", "refit_buffers", "triangles_of",
     "AtomicReference", "FrameData", "HipEngine", "Renderer",
 ]

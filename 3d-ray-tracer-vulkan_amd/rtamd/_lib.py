@@ -46,13 +46,14 @@ EXPORTED = (
     "rt_render_temporal_variance",
     "rt_learn_device", "rt_learn_copy",
     "rt_samples_workspace_bytes", "rt_render_samples_device", "rt_render_samples",
+    "rt_update_geometry", "rt_refit_scene", "rt_accel_refit_records", "rt_scene_copy_records",
 )
 
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
 # "src=" field is the first 16 hex digits of SHA-256 over them concatenated.
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
                  "csrc/rt_denoise.hip", "csrc/rt_denoise_history.hip", "csrc/rt_temporal.hip", "csrc/rt_variance.hip",
-                 "csrc/rt_samples.hip", "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h",
+                 "csrc/rt_samples.hip", "csrc/rt_refit.hip", "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h",
                  "csrc/accel_build.h", "../include/rtamd.h")
 
 
@@ -271,6 +272,10 @@ def lib() -> C.CDLL:
                 "rt_render_samples_device": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, i32, vp, sz, vp, vp, vp, vp,
                                                    C.POINTER(Stats)]),
                 "rt_render_samples": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, i32, vp, vp, C.POINTER(Stats)]),
+                "rt_update_geometry": (i32, [vp, vp, sz, vp, sz, dp]),
+                "rt_refit_scene": (i32, [dp, sz, C.POINTER(C.c_uint32), sz, fp, vp, sz]),
+                "rt_accel_refit_records": (i32, [C.POINTER(C.c_uint32), sz, i32, vp, sz, vp, sz]),
+                "rt_scene_copy_records": (i32, [vp, i32, C.POINTER(C.c_uint32), sz, C.POINTER(sz)]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)
@@ -319,3 +324,16 @@ def accel_records(built, n_layouts: int = 8, half: bool = False, wide: bool = Fa
     d = dict(zip(keys, list(info)))
     d["format"] = 1 if half else (2 if wide else 0)
     return out, d
+
+
+def accel_refit_records(records, n_layouts: int, built):
+    """rt_accel_refit_records: a refitted copy of format-0 accel records
+    (accel_records' words for n_layouts 1 or 8) for the moved vertices and the
+    new boxes of `built`.  Host-only."""
+    import numpy as np
+    out = np.array(records, dtype=np.uint32, copy=True)
+    v = np.ascontiguousarray(built.model_vertex_data)
+    b = np.ascontiguousarray(built.flat_bvh_data)
+    check(lib().rt_accel_refit_records(out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, n_layouts,
+                                       v.ctypes.data, v.nbytes, b.ctypes.data, b.nbytes))
+    return out

@@ -104,6 +104,31 @@ class Renderer:
         check(lib().rt_upload_scene(self._ctx, v.ctypes.data, v.nbytes, m.ctypes.data, m.nbytes,
                                     b.ctypes.data, b.nbytes))
 
+    def update_geometry(self, built: BuiltCpuData, ms: bool = False):
+        """rt_update_geometry: the scene's triangles moved, in the tree it was
+        uploaded with (option "refit" 1 at that upload).  built: the moved
+        vertex records and the uploaded nodes with new boxes
+        (rtamd.refit_buffers).  Returns the refit kernels' device time in ms
+        with ms=True, else None."""
+        v = np.ascontiguousarray(built.model_vertex_data, dtype=np.float32)
+        b = np.ascontiguousarray(built.flat_bvh_data, dtype=np.uint8)
+        t = C.c_double()
+        check(lib().rt_update_geometry(self._ctx, v.ctypes.data, v.nbytes, b.ctypes.data, b.nbytes,
+                                       C.byref(t) if ms else None))
+        return t.value if ms else None
+
+    def copy_records(self, which: int) -> np.ndarray:
+        """rt_scene_copy_records: one of the scene's device arrays as uint32
+        words (0 walk, 1 walk_ref, 2 shading, 3 nodes, 4 leafs, 5 pairs; empty
+        when the scene holds none).  A diagnostic: it waits for the device."""
+        n = C.c_size_t()
+        check(lib().rt_scene_copy_records(self._ctx, which, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            check(lib().rt_scene_copy_records(self._ctx, which, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size,
+                                              C.byref(n)))
+        return out
+
     def upload_spheres(self, spheres) -> None:
         """Extension (option "extensions" bit 8; no reference counterpart):
         float32[n, 8] = (centre.xyz, radius, albedo.rgb, type); n = 0 removes

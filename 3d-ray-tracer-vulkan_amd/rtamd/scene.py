@@ -244,6 +244,25 @@ def build_buffers(tri_verts: np.ndarray, tri_mats: np.ndarray, axis_seed: int = 
     return BuiltCpuData(v, m, b, nf.value, src)
 
 
+def refit_buffers(built: BuiltCpuData, tri_verts: np.ndarray) -> BuiltCpuData:
+    """The buffers of `built` (from build_buffers) for moved input triangles, in
+    the same tree (rt_refit_scene): the vertex records and every box are the
+    builder's own for tri_verts, the links, the materials and flat_source are
+    built's.  What Renderer.update_geometry takes."""
+    tri_verts = np.ascontiguousarray(tri_verts, dtype=np.float64).reshape(-1, 9)
+    if built.triangle_count == 0:              # the empty scene's dummies
+        return BuiltCpuData(built.model_vertex_data.copy(), built.model_material_data, built.flat_bvh_data.copy(), 0,
+                            built.flat_source)
+    if built.flat_source is None:
+        raise ValueError("these buffers carry no flat_source (not made by build_buffers)")
+    src = np.ascontiguousarray(built.flat_source, dtype=np.uint32)
+    v = np.empty(src.size * 12, dtype=np.float32)
+    b = np.array(built.flat_bvh_data, dtype=np.uint8, copy=True)
+    check(lib().rt_refit_scene(_dptr(tri_verts), tri_verts.shape[0], src.ctypes.data_as(C.POINTER(C.c_uint32)), src.size,
+                               _fptr(v), b.ctypes.data_as(C.c_void_p), b.size // 48))
+    return BuiltCpuData(v, built.model_material_data, b, built.triangle_count, built.flat_source)
+
+
 def instance_of(scene: Scene, built: BuiltCpuData, tri: int) -> ModelInstance:
     """The ModelInstance a flattened triangle index (rt_hit.tri, Renderer.pick)
     came from: built.flat_source names the input triangle, and the inputs are

@@ -261,6 +261,78 @@ int rt_render_wait(rt_ctx* ctx, uint64_t ticket);
  * of blocking its thread. */
 int rt_render_poll(rt_ctx* ctx, uint64_t ticket, int* done);
 
+/* ------------------------------------------------------------------ refit -- */
+/* Moved triangles without a new upload: the tree keeps its
+ * shape, and every box and every triangle record of the scene is recomputed
+ * on the device from the moved vertices.  Needs a scene uploaded with option
+ * "refit" 1.  Added at ABI version 6 without a bump: no existing struct or
+ * argument list changed.
+ *
+ * vertices : the moved triangles, in the flattened order and byte size of the
+ *            uploaded scene.
+ * bvh_nodes: the uploaded node array with new boxes; every byte of every node
+ *            outside its two boxes (offsets 0-11 and 16-27) must equal the
+ *            uploaded node's (checked against a host copy kept at upload).
+ * Materials do not change.  rt_refit_scene produces both buffers.
+ * Synchronous, host pointers.  Afterwards every render, query, first-hit
+ * buffer and pick of the context equals, bit for bit, what a fresh context
+ * gives after rt_upload_scene(vertices, the uploaded materials, bvh_nodes):
+ * RGBA8, radiance, hit records, segments and mat_reads; node_visits and
+ * tri_tests are those of the walk over the refitted records (on the accel
+ * tree: rt_accel_refit_records' of the uploaded scene's records).  The call
+ * waits for every device of the context, refits each of them, drops the
+ * temporal history and the samples sum as rt_upload_scene does, and keeps the
+ * learned tile orders and heavy pixels (results never depend on them).
+ * ms (nullable): the device time of the refit kernels on device 0 (HIP events).
+ * Errors, the scene unchanged in every case: RT_ERR_NO_SCENE;
+ * RT_ERR_INVALID_ARG for a null pointer or a scene without refit tables
+ * (option "refit" 0, or the accel_half / accel_wide record formats);
+ * RT_ERR_BAD_SCENE for a wrong size, a node byte outside the boxes that
+ * differs, a non-finite vertex or box, or a triangle the accel build dropped
+ * as a byte-identical duplicate whose new vertex record or leaf box is no
+ * longer byte-identical to its keeper's. */
+int rt_update_geometry(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
+                       const void* bvh_nodes, size_t bvh_bytes, double* ms);
+
+/* The two buffers rt_update_geometry takes, from moved input triangles (pure
+ * host code).  tri_verts: n_tris*9 doubles as rt_build_scene_map took them;
+ * source: its out_source (n_flat entries); out_vertices: n_flat*12 floats;
+ * nodes_inout: the n_nodes*48 bytes rt_build_scene_map wrote, whose boxes are
+ * rewritten and whose links are left alone.  Flattened triangle f becomes the
+ * float cast of input triangle source[f]; a leaf's box is
+ * Triangle.calculateBoundingBox (Triangle.java:61-71) of its triangle in
+ * double, an internal node's AABB.surroundingBox of its children's double
+ * boxes, bottom-up, each cast to float once: the bytes the builder itself
+ * writes for these triangles in this tree. */
+int rt_refit_scene(const double* tri_verts, size_t n_tris, const uint32_t* source, size_t n_flat,
+                   float* out_vertices, void* nodes_inout, size_t n_nodes);
+
+/* What the device does to format-0 accel records, on the CPU (pure host code):
+ * words_inout holds rt_accel_records' output for n_layouts 1 or 8.  Every leaf
+ * slot pair, with tri = word 3 & (2^29 - 1), takes the box of the reference
+ * leaf that names tri (words 0-2, 4-6), v0 / e1 / e2 (words 7-15; e1 and e2
+ * unfused binary32 differences) and bit 29 of word 3 exactly when its shape
+ * class is >= 7.  Every internal slot takes the union of its two children's
+ * boxes (min / max that keep the lower-centroid child's value on a tie, so
+ * signed zeros are the builder's) and the OR of their bits 29.  Every other
+ * bit stays.  RT_ERR_BAD_SCENE: buffers rt_scene_validate refuses, two leaves
+ * naming one triangle, or words that are not such records; RT_ERR_INVALID_ARG:
+ * a null pointer, n_layouts not 1 or 8, n_words not 8 * n_layouts * slots + 16. */
+int rt_accel_refit_records(uint32_t* words_inout, size_t n_words, int n_layouts,
+                           const void* vertices, size_t vertex_bytes, const void* bvh_nodes, size_t bvh_bytes);
+
+/* Diagnostic, in the style of rt_diag_copy: waits for device 0 and copies one
+ * of the device arrays rt_update_geometry rewrites, as 32-bit words.  which:
+ * 0 = the walk records (the accel records, or with accel 0 the reference's),
+ * 1 = the reference's walk records beside the accel records, 2 = the shading
+ * records (normal, material: 8 words per triangle), 3 / 4 / 5 = the node,
+ * leaf and pair arrays of accel 0 (8 / 12 / 16 words per node of the root's
+ * subtree).  Copies up to cap_words words (out_words may be NULL to size the
+ * call); *n_words = the array's words, 0 for an array the scene does not hold.
+ * For a freshly uploaded accel scene, which 0 equals rt_accel_records' words.
+ * Not for timing runs. */
+int rt_scene_copy_records(rt_ctx* ctx, int which, uint32_t* out_words, size_t cap_words, size_t* n_words);
+
 /* ---------------------------------------------------------------- queries -- */
 /* Ray queries: the walk of one segment of the shader's bounce loop
  * (compute_dynamic_ray.comp:181-213), returning the hit instead of shading it.
@@ -934,6 +1006,21 @@ int rt_render_samples(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int heig
  *                   the 8 XCDs), else packed
  *   "leaf_align_used" (rt_get_option only) 1 if the current scene's records
  *                   on device 0 hold pad slots
+ *   "refit"         at the next rt_upload_scene: 1 = keep what rt_update_geometry
+ *                   needs, on the host (24 B per node, the links; 16 B per
+ *                   dropped duplicate) and on every device: a staging buffer
+ *                   of 48 B per flattened triangle + 24 B per node, 8 B per
+ *                   node of tables, and on the accel tree 48 + 4 x layouts B
+ *                   per tree node and 12 B per kept triangle.  Per flattened
+ *                   triangle of a built scene that is 234 B (config 3) to
+ *                   265 B (config 5) with 8 layouts, 15 MB and 277 MB in all,
+ *                   and about 110 B on the reference's tree ("refit_bytes"
+ *                   says exactly).  0 (default) = the upload's
+ *                   time and memory are what they always were.  Scenes
+ *                   uploaded with accel_half or accel_wide never hold the
+ *                   tables.  0 / 1
+ *   "refit_used"    (rt_get_option only) 1 when the current scene holds them
+ *   "refit_bytes"   (rt_get_option only) the device bytes they take on device 0
  *   "plain_kernels" (rt_get_option only) production-build trace kernels enqueued
  *                   on device 0 so far (not counting, diagnostic or learning
  *                   launches, nor query launches): lets a profiler's kernel trace be cut at a

@@ -196,6 +196,28 @@ JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_renderTemporal(JNI
     if (rc) throw_rt(env, rc);
 }
 
+/* void updateGeometry(long ctx, ByteBuffer vertices, ByteBuffer nodes)
+ * The scene's triangles moved, in the tree it was uploaded with (rtamd.h rt_update_geometry; the scene must have
+ * been uploaded after setOption(ctx, "refit", 1)).  Direct buffers whose capacities are the byte sizes: the moved
+ * vertex records in the uploaded order and the uploaded nodes with new boxes.  Synchronous; on the thread that
+ * owns ctx. */
+JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_updateGeometry(JNIEnv* env, jclass c, jlong ctx,
+        jobject vertices, jobject nodes) {
+    /* a heap (non-direct) buffer has capacity -1 */
+    if (!vertices || !nodes || (*env)->GetDirectBufferCapacity(env, vertices) < 0 ||
+        (*env)->GetDirectBufferCapacity(env, nodes) < 0) {
+        jclass ex = (*env)->FindClass(env, "java/lang/RuntimeException");
+        if (ex) (*env)->ThrowNew(env, ex, "updateGeometry: need direct buffers (the vertex records and the nodes)");
+        return;
+    }
+    int rc = rt_update_geometry((rt_ctx*)(intptr_t)ctx,
+                                (*env)->GetDirectBufferAddress(env, vertices),
+                                (size_t)(*env)->GetDirectBufferCapacity(env, vertices),
+                                (*env)->GetDirectBufferAddress(env, nodes),
+                                (size_t)(*env)->GetDirectBufferCapacity(env, nodes), NULL);
+    if (rc) throw_rt(env, rc);
+}
+
 JNIEXPORT void JNICALL Java_dev_demir_vulkan_engine_HipNative_destroy(JNIEnv* env, jclass c, jlong ctx) {
     rt_destroy((rt_ctx*)(intptr_t)ctx);
 }

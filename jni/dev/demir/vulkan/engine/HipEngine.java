@@ -24,6 +24,8 @@ public class HipEngine implements Runnable {
     private final ByteBuffer ubo = ByteBuffer.allocateDirect(80).order(ByteOrder.nativeOrder());
     private final ByteBuffer hit = ByteBuffer.allocateDirect(32).order(ByteOrder.nativeOrder());   // rt_hit
     private final ConcurrentLinkedQueue<Object[]> pickQueue = new ConcurrentLinkedQueue<>();
+    private final ConcurrentLinkedQueue<ByteBuffer[]> geometryQueue = new ConcurrentLinkedQueue<>();
+    private volatile boolean refit = false;                               // setRefit: uploads keep the refit tables
     private long ctx = 0;
     private boolean haveScene = false;
     private ByteBuffer[] slots = null;
@@ -53,6 +55,15 @@ public class HipEngine implements Runnable {
     public void submitScene(BuiltCpuData d) { sceneQueue.add(d); }
     public void submitCameraUpdate(Camera c) { cameraQueue.add(c); }
     public void submitSkyToggle(boolean on) { skyToggleQueue.add(on); }
+    /** Scenes submitted from now on keep what submitGeometryUpdate needs (rt option "refit"). */
+    public void setRefit(boolean on) { refit = on; }
+    /** The current scene's triangles moved (an object dragged): the moved vertex records in the uploaded order and
+     *  the uploaded nodes with new boxes, as direct buffers whose capacities are their byte sizes (rt_refit_scene
+     *  writes both).  Applied on the render thread before its next frame (rt_update_geometry); only the newest
+     *  of several pending updates is applied.  The scene must have been submitted after setRefit(true). */
+    public void submitGeometryUpdate(ByteBuffer vertices, ByteBuffer nodes) {
+        geometryQueue.add(new ByteBuffer[]{vertices, nodes});
+    }
     /** The flattened triangle under pixel (x, y) of the current camera (negative: nothing), handed to onHit
      *  on the render thread, which owns the context (rt_pick; a context is single-thread-affine). */
     public void submitPick(int x, int y, java.util.function.IntConsumer onHit) {
@@ -89,12 +100,22 @@ public class HipEngine implements Runnable {
             while (isRunning) {
                 BuiltCpuData d = sceneQueue.poll();                       // one scene per pass (:281-285)
                 if (d != null) {
+                    geometryQueue.clear();                                // updates of the scene this one replaces
+                    HipNative.setOption(ctx, "refit", refit ? 1 : 0);
                     HipNative.uploadScene(ctx, memByteBufferOf(d.modelVertexData), d.modelVertexData.remaining() * 4L,
                                           memByteBufferOf(d.modelMaterialData), d.modelMaterialData.remaining() * 4L,
                                           d.flatBvhData, d.flatBvhData.remaining());
                     memFree(d.modelVertexData);                           // as VulkanEngine.java:343,351
                     memFree(d.modelMaterialData);
                     haveScene = true;
+                }
+                ByteBuffer[] g, moved = null;                             // drain to the latest, like the cameras
+                while ((g = geometryQueue.poll()) != null) moved = g;
+                if (moved != null && haveScene) {
+                    for (int j = 0; j < IN_FLIGHT; j++)                   // frames in flight read the old records
+                        if (tickets[j] != 0) { HipNative.waitFrame(ctx, tickets[j]); tickets[j] = 0; }
+                    submitted = 0;
+                    HipNative.updateGeometry(ctx, moved[0], moved[1]);
                 }
                 Camera c, latest = null;                                  // drain to the latest (:288-298)
                 while ((c = cameraQueue.poll()) != null) latest = c;

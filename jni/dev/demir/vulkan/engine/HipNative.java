@@ -34,4 +34,9 @@ final class HipNative {
     static native void renderTemporal(long ctx, ByteBuffer ubo80, int w, int h, int maxBounces, int maxHistory,
                                       float planeTol, float normalMin, int filterIterations, int flags,
                                       ByteBuffer outRgba);
+    /** rt_update_geometry: the uploaded scene's triangles moved, in the tree it was uploaded with (the upload must
+     *  follow setOption(ctx, "refit", 1)).  Direct buffers whose capacities are the byte sizes: the moved vertex
+     *  records in the uploaded order, and the uploaded nodes with new boxes (rt_refit_scene writes both).
+     *  Synchronous; on the thread that owns ctx. */
+    static native void updateGeometry(long ctx, ByteBuffer vertices, ByteBuffer nodes);
 }
