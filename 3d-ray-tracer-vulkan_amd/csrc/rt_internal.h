@@ -296,29 +296,36 @@ void set_error(const char* fmt, ...);
 hipError_t wire_pack(const void* rgba, void* rgb, size_t n_px, hipStream_t s);
 hipError_t wire_unpack(const void* rgb, void* rgba, size_t n_px, hipStream_t s);
 
-// rt_denoise.hip: the a-trous filter's passes (rtamd.h rt_denoise_device,
-// DESIGN.md §4g), enqueued on `stream`; validated arguments, nothing allocated.
-struct DenoiseArgs {
+// rt_filter.hip: an a-trous filter's passes (rtamd.h rt_denoise_device,
+// rt_denoise_history_device and rt_denoise_variance_device; DESIGN.md §4g, §4i,
+// §4j), enqueued on `stream`; validated arguments, nothing allocated.
+enum FilterKind { kFilterRadiance = 0, kFilterHistory = 1, kFilterVariance = 2 };
+struct FilterArgs {
+    FilterKind    kind;
     int           width, height;
-    const float*  radiance;     // the render's radiance, 3 floats per pixel
+    const float*  radiance;     // Radiance: the render's radiance, 3 floats per pixel (else null)
+    const float4* hist;         // History, Variance: (c.rgb, n) per pixel (else null)
+    const float2* mom;          // Variance: (m1, m2) per pixel (else null)
     const float4* hits;         // rt_hit records, 2 float4 per pixel
-    float4*       workspace;    // 2 x width x height float4
+    float4*       workspace;    // 2 x width x height float4: a pass's records
     uchar4*       out_rgba;     // nullable
     float*        out_rad;      // nullable
     int           iterations, normal_power_log2;
-    float         sigma_depth, inv_sigma_color;   // 1.0f / sigma_color, computed in float on the host
+    int           min_history;  // Variance
+    float         sigma_depth;
+    float         tolerance;    // Radiance, History: 1.0f / sigma_color, computed in float on the host;
+                                //   Variance: sigma_lum
     int           form;         // option denoise_kernel: 0 = the measured choice per step, 1 = plain, 2 = tiled
-    int           only_pass;    // option denoise_pass: -1 = every pass, i = pass i alone (timing)
+                                //   (Variance: tiled at step 1 alone)
+    int           only_pass;    // option denoise_pass: -1 = every pass (Variance: behind the estimate),
+                                //   i = pass i alone (timing)
+    int           stage;        // Variance, option variance_stage: -1 = everything, 0 = the estimate alone (timing)
 };
-hipError_t launch_denoise(const DenoiseArgs& d, hipStream_t stream);
-// rt_denoise_history.hip: the history-adaptive filter's passes (rtamd.h
-// rt_denoise_history_device) on `hist`, width x height records
-// (c.rgb, n); d.radiance is not read.
-hipError_t launch_denoise_history(const DenoiseArgs& d, const float4* hist, hipStream_t stream);
+hipError_t launch_filter(const FilterArgs& d, hipStream_t stream);
 
 // rt_temporal.hip: the temporal accumulation's one kernel (rtamd.h
-// rt_temporal_device), enqueued on `stream`; validated
-// arguments, nothing allocated.
+// rt_temporal_device and rt_temporal_moments_device),
+// enqueued on `stream`; validated arguments, nothing allocated.
 struct TemporalBasis {          // rt_temporal_camera_basis's 13 floats
     float ox, oy, oz;           // origin
     float nx, ny, nz;           // N = cross(horizontal, vertical)
@@ -338,29 +345,12 @@ struct TemporalArgs {
     uchar4*       out_rgba;     // nullable
     float*        out_rad;      // nullable
     int           form;         // option temporal_tile: 0 = the shipped form, 1 = 64 x 1 waves, 2 = 16 x 4
+    // the luminance moments (m1, m2) per pixel beside the history: mom_out null = none are kept;
+    // mom_prev is null exactly when hist_prev is
+    const float2* mom_prev;
+    float2*       mom_out;
 };
 hipError_t launch_temporal(const TemporalArgs& t, hipStream_t stream);
-
-// rt_variance.hip: the accumulation with luminance moments and the
-// variance-guided filter (rtamd.h rt_temporal_moments_device and
-// rt_denoise_variance_device), enqueued on `stream`; validated
-// arguments, nothing allocated.  mom_prev is null exactly when t.hist_prev is.
-hipError_t launch_temporal_moments(const TemporalArgs& t, const float2* mom_prev, float2* mom_out, hipStream_t stream);
-struct VarianceArgs {
-    int           width, height;
-    const float4* hist;         // (c.rgb, n) per pixel
-    const float2* mom;          // (m1, m2) per pixel
-    const float4* hits;         // rt_hit records, 2 float4 per pixel
-    float4*       workspace;    // 2 x width x height float4: records (c.rgb, v)
-    uchar4*       out_rgba;     // nullable
-    float*        out_rad;      // nullable
-    int           iterations, normal_power_log2, min_history;
-    float         sigma_depth, sigma_lum;
-    int           form;         // option denoise_kernel: 0 = the measured choice at step 1, 1 = plain, 2 = tiled at step 1
-    int           only_pass;    // option denoise_pass: -1 = the estimate and every pass, i = pass i alone (timing)
-    int           stage;        // option variance_stage: -1 = everything, 0 = the estimate alone (timing)
-};
-hipError_t launch_denoise_variance(const VarianceArgs& d, hipStream_t stream);
 
 // rt_samples.hip: folds the linear-colour frames of one samples launch into
 // the running sum, in frame order (rtamd.h rt_render_samples_device, DESIGN.md

@@ -459,7 +459,7 @@ struct rt_ctx {
                                    //   half precision (accel_build.h)
     int  accel_wide = 0;           // at the next upload: the 4-wide tree, format 2 (overrides accel_half)
     int  denoise_kernel = 0;       // rt_denoise_device: 0 = per step size the form measured faster, 1 = the
-                                   //   plain form, 2 = the tiled form (rt_denoise.hip; same results)
+                                   //   plain form, 2 = the tiled form (rt_filter.hip; same results)
     int  denoise_pass = -1;        // rt_denoise_device: i >= 0 = enqueue pass i alone (tools/denoise_bench.py)
     int  temporal_tile = 0;        // rt_temporal_device: 0 = the lane mapping measured faster, 1 = a wave on 64
                                    //   pixels of a row, 2 = on a 16x4 tile (rt_temporal.hip; same results)
@@ -2178,6 +2178,45 @@ static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     return x < y + nb && y < x + na;
 }
 
+// One device buffer of a call that works on the caller's memory, as its checks see it.
+enum BufRole { kBufIn, kBufOut, kBufWorkspace };
+struct Buf {
+    const void* p;
+    size_t      bytes;
+    unsigned    align;      // a power of two
+    const char* name;
+    BufRole     role;
+    bool        nullable;
+};
+
+// The checks every such call makes on its buffers: none null that must be given (the refusal says
+// `what_null`), each on its alignment, no output on an input, a workspace or an earlier output, no
+// workspace on an input.  Null buffers are skipped.
+static int check_buffers(const char* fn, const char* what_null, const Buf* b, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!b[i].p && !b[i].nullable) {
+            set_error("%s: null %s", fn, what_null);
+            return RT_ERR_INVALID_ARG;
+        }
+    for (int i = 0; i < n; ++i)
+        if ((uintptr_t)b[i].p & (b[i].align - 1u)) {
+            set_error("%s: %s must be %u-byte aligned", fn, b[i].name, b[i].align);
+            return RT_ERR_INVALID_ARG;
+        }
+    for (int i = 0; i < n; ++i) {
+        if (!b[i].p || b[i].role == kBufIn) continue;
+        for (int j = 0; j < n; ++j) {
+            // an input, or the output or workspace listed earlier (each pair once)
+            if (!b[j].p || j == i || (b[j].role != kBufIn && j > i)) continue;
+            if (ranges_overlap(b[i].p, b[i].bytes, b[j].p, b[j].bytes)) {
+                set_error("%s: %s overlaps %s", fn, b[i].name, b[j].name);
+                return RT_ERR_INVALID_ARG;
+            }
+        }
+    }
+    return RT_OK;
+}
+
 static int check_denoise_params(const rt_denoise_params* q, const char* fn) {
     if (q->iterations < 1 || q->iterations > 6 || q->normal_power_log2 < 0 || q->normal_power_log2 > 10) {
         set_error("%s: iterations must be in [1, 6] and normal_power_log2 in [0, 10], got %d and %d", fn,
@@ -2191,86 +2230,6 @@ static int check_denoise_params(const rt_denoise_params* q, const char* fn) {
         return RT_ERR_INVALID_ARG;
     }
     return RT_OK;
-}
-
-// rt_denoise_device (d_in = the render's radiance, 12 B per pixel) and rt_denoise_history_device (d_in = a
-// history buffer, 16 B per pixel, 16-byte aligned): the same checks, workspace and passes' timing.
-static int denoise_device(const char* fn, bool history, rt_ctx* ctx, int width, int height, const void* d_in,
-                          const rt_hit* d_hits, const rt_denoise_params* params, void* d_workspace, void* d_out_rgba,
-                          float* d_out_radiance, void* stream, double* ms) {
-    if (!ctx || !d_in || !d_hits || !d_workspace) {
-        set_error("%s: null context or buffer", fn);
-        return RT_ERR_INVALID_ARG;
-    }
-    if (!d_out_rgba && !d_out_radiance) { set_error("%s: both outputs are null", fn); return RT_ERR_INVALID_ARG; }
-    const size_t ws_bytes = rt_denoise_workspace_bytes(width, height);
-    if (ws_bytes == 0) { set_error("%s: bad frame size %dx%d", fn, width, height); return RT_ERR_INVALID_ARG; }
-    rt_denoise_params q;
-    rt_denoise_default_params(&q);
-    if (params) q = *params;
-    if (int rc = check_denoise_params(&q, fn)) return rc;
-    if ((((uintptr_t)d_hits | (uintptr_t)d_workspace) & 15u) || ((uintptr_t)d_in & (history ? 15u : 3u)) ||
-        (((uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
-        set_error(history ? "%s: d_hist, d_hits and d_workspace must be 16-byte aligned, the other buffers 4-byte"
-                          : "%s: d_hits and d_workspace must be 16-byte aligned, the other buffers 4-byte", fn);
-        return RT_ERR_INVALID_ARG;
-    }
-    const size_t px = (size_t)width * (size_t)height;
-    const struct { const void* p; size_t n; const char* name; } in[3] = {
-        {d_in, px * (history ? 16 : 12), history ? "d_hist" : "d_radiance"}, {d_hits, px * 32, "d_hits"},
-        {d_workspace, ws_bytes, "d_workspace"}};
-    const struct { const void* p; size_t n; const char* name; } out[2] = {
-        {d_out_rgba, px * 4, "d_out_rgba"}, {d_out_radiance, px * 12, "d_out_radiance"}};
-    for (const auto& o : out) {
-        if (!o.p) continue;
-        for (const auto& i : in)
-            if (ranges_overlap(o.p, o.n, i.p, i.n)) {
-                set_error("%s: %s overlaps %s", fn, o.name, i.name);
-                return RT_ERR_INVALID_ARG;
-            }
-    }
-    if (d_out_rgba && d_out_radiance && ranges_overlap(out[0].p, out[0].n, out[1].p, out[1].n)) {
-        set_error("%s: d_out_rgba overlaps d_out_radiance", fn);
-        return RT_ERR_INVALID_ARG;
-    }
-    for (int k = 0; k < 2; ++k)
-        if (ranges_overlap(in[2].p, in[2].n, in[k].p, in[k].n)) {
-            set_error("%s: d_workspace overlaps %s", fn, in[k].name);
-            return RT_ERR_INVALID_ARG;
-        }
-    PerDevice& p = ctx->dev[0];
-    RT_HIP_CHECK(hipSetDevice(p.device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DenoiseArgs d;
-    d.width = width; d.height = height;
-    d.radiance = history ? nullptr : static_cast<const float*>(d_in);
-    d.hits = reinterpret_cast<const float4*>(d_hits);
-    d.workspace = static_cast<float4*>(d_workspace);
-    d.out_rgba = static_cast<uchar4*>(d_out_rgba);
-    d.out_rad = d_out_radiance;
-    d.iterations = q.iterations;
-    d.normal_power_log2 = q.normal_power_log2;
-    d.sigma_depth = q.sigma_depth;
-    d.inv_sigma_color = 1.0f / q.sigma_color;
-    d.form = ctx->denoise_kernel;
-    d.only_pass = ctx->denoise_pass < q.iterations ? ctx->denoise_pass : -1;
-    if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
-    RT_HIP_CHECK(history ? launch_denoise_history(d, static_cast<const float4*>(d_in), s) : launch_denoise(d, s));
-    return ms ? elapsed_ms(p, s, ms) : RT_OK;
-}
-
-int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radiance, const rt_hit* d_hits,
-                      const rt_denoise_params* params, void* d_workspace, void* d_out_rgba, float* d_out_radiance,
-                      void* stream, double* ms) {
-    return denoise_device("rt_denoise_device", false, ctx, width, height, d_radiance, d_hits, params, d_workspace,
-                          d_out_rgba, d_out_radiance, stream, ms);
-}
-
-int rt_denoise_history_device(rt_ctx* ctx, int width, int height, const void* d_hist, const rt_hit* d_hits,
-                              const rt_denoise_params* params, void* d_workspace, void* d_out_rgba,
-                              float* d_out_radiance, void* stream, double* ms) {
-    return denoise_device("rt_denoise_history_device", true, ctx, width, height, d_hist, d_hits, params, d_workspace,
-                          d_out_rgba, d_out_radiance, stream, ms);
 }
 
 static int check_variance_params(const rt_variance_params* q, const char* fn) {
@@ -2292,73 +2251,84 @@ static int check_variance_params(const rt_variance_params* q, const char* fn) {
     return RT_OK;
 }
 
-// rt_denoise_history_device's checks with the moments as a third read-only input.
-int rt_denoise_variance_device(rt_ctx* ctx, int width, int height, const void* d_hist, const void* d_mom,
-                               const rt_hit* d_hits, const rt_variance_params* params, void* d_workspace,
-                               void* d_out_rgba, float* d_out_radiance, void* stream, double* ms) {
-    const char* const fn = "rt_denoise_variance_device";
-    if (!ctx || !d_hist || !d_mom || !d_hits || !d_workspace) {
-        set_error("%s: null context or buffer", fn);
-        return RT_ERR_INVALID_ARG;
-    }
-    if (!d_out_rgba && !d_out_radiance) { set_error("%s: both outputs are null", fn); return RT_ERR_INVALID_ARG; }
+// rt_denoise_device (d_in = the render's radiance, 12 B per pixel), rt_denoise_history_device (d_in = a
+// history buffer, 16 B per pixel) and rt_denoise_variance_device (d_in = a history buffer, d_mom = its
+// moments, 8 B per pixel; vparams in place of params): the same checks, workspace and passes' timing.
+static int denoise_device(const char* fn, FilterKind kind, rt_ctx* ctx, int width, int height, const void* d_in,
+                          const void* d_mom, const rt_hit* d_hits, const rt_denoise_params* params,
+                          const rt_variance_params* vparams, void* d_workspace, void* d_out_rgba,
+                          float* d_out_radiance, void* stream, double* ms) {
+    const bool variance = kind == kFilterVariance;
+    if (!ctx) { set_error("%s: null context or buffer", fn); return RT_ERR_INVALID_ARG; }
     const size_t ws_bytes = rt_denoise_workspace_bytes(width, height);
+    const size_t px = ws_bytes / 32;
+    const Buf bufs[6] = {
+        {d_in, px * (kind == kFilterRadiance ? 12 : 16), kind == kFilterRadiance ? 4u : 16u,
+         kind == kFilterRadiance ? "d_radiance" : "d_hist", kBufIn, false},
+        {d_mom, px * 8, 8, "d_mom", kBufIn, !variance},
+        {d_hits, px * 32, 16, "d_hits", kBufIn, false},
+        {d_workspace, ws_bytes, 16, "d_workspace", kBufWorkspace, false},
+        {d_out_rgba, px * 4, 4, "d_out_rgba", kBufOut, true},
+        {d_out_radiance, px * 12, 4, "d_out_radiance", kBufOut, true}};
+    if (!d_out_rgba && !d_out_radiance) { set_error("%s: both outputs are null", fn); return RT_ERR_INVALID_ARG; }
     if (ws_bytes == 0) { set_error("%s: bad frame size %dx%d", fn, width, height); return RT_ERR_INVALID_ARG; }
-    rt_variance_params q;
-    rt_variance_default_params(&q);
-    if (params) q = *params;
-    if (int rc = check_variance_params(&q, fn)) return rc;
-    if ((((uintptr_t)d_hits | (uintptr_t)d_workspace | (uintptr_t)d_hist) & 15u) || ((uintptr_t)d_mom & 7u) ||
-        (((uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
-        set_error("%s: d_hist, d_hits and d_workspace must be 16-byte aligned, d_mom 8-byte, the other buffers 4-byte",
-                  fn);
-        return RT_ERR_INVALID_ARG;
+    rt_denoise_params q;
+    rt_denoise_default_params(&q);
+    rt_variance_params v;
+    rt_variance_default_params(&v);
+    if (variance) {
+        if (vparams) v = *vparams;
+        if (int rc = check_variance_params(&v, fn)) return rc;
+    } else {
+        if (params) q = *params;
+        if (int rc = check_denoise_params(&q, fn)) return rc;
     }
-    const size_t px = (size_t)width * (size_t)height;
-    const struct { const void* p; size_t n; const char* name; } in[4] = {
-        {d_hist, px * 16, "d_hist"}, {d_mom, px * 8, "d_mom"}, {d_hits, px * 32, "d_hits"},
-        {d_workspace, ws_bytes, "d_workspace"}};
-    const struct { const void* p; size_t n; const char* name; } out[2] = {
-        {d_out_rgba, px * 4, "d_out_rgba"}, {d_out_radiance, px * 12, "d_out_radiance"}};
-    for (const auto& o : out) {
-        if (!o.p) continue;
-        for (const auto& i : in)
-            if (ranges_overlap(o.p, o.n, i.p, i.n)) {
-                set_error("%s: %s overlaps %s", fn, o.name, i.name);
-                return RT_ERR_INVALID_ARG;
-            }
-    }
-    if (d_out_rgba && d_out_radiance && ranges_overlap(out[0].p, out[0].n, out[1].p, out[1].n)) {
-        set_error("%s: d_out_rgba overlaps d_out_radiance", fn);
-        return RT_ERR_INVALID_ARG;
-    }
-    for (int k = 0; k < 3; ++k)
-        if (ranges_overlap(in[3].p, in[3].n, in[k].p, in[k].n)) {
-            set_error("%s: d_workspace overlaps %s", fn, in[k].name);
-            return RT_ERR_INVALID_ARG;
-        }
+    if (int rc = check_buffers(fn, "context or buffer", bufs, 6)) return rc;
     PerDevice& p = ctx->dev[0];
     RT_HIP_CHECK(hipSetDevice(p.device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    VarianceArgs d;
+    FilterArgs d;
+    d.kind = kind;
     d.width = width; d.height = height;
-    d.hist = static_cast<const float4*>(d_hist);
+    d.radiance = kind == kFilterRadiance ? static_cast<const float*>(d_in) : nullptr;
+    d.hist = kind == kFilterRadiance ? nullptr : static_cast<const float4*>(d_in);
     d.mom = static_cast<const float2*>(d_mom);
     d.hits = reinterpret_cast<const float4*>(d_hits);
     d.workspace = static_cast<float4*>(d_workspace);
     d.out_rgba = static_cast<uchar4*>(d_out_rgba);
     d.out_rad = d_out_radiance;
-    d.iterations = q.iterations;
-    d.normal_power_log2 = q.normal_power_log2;
-    d.min_history = q.min_history;
-    d.sigma_depth = q.sigma_depth;
-    d.sigma_lum = q.sigma_lum;
+    d.iterations = variance ? v.iterations : q.iterations;
+    d.normal_power_log2 = variance ? v.normal_power_log2 : q.normal_power_log2;
+    d.min_history = v.min_history;
+    d.sigma_depth = variance ? v.sigma_depth : q.sigma_depth;
+    d.tolerance = variance ? v.sigma_lum : 1.0f / q.sigma_color;
     d.form = ctx->denoise_kernel;
-    d.only_pass = ctx->denoise_pass < q.iterations ? ctx->denoise_pass : -1;
+    d.only_pass = ctx->denoise_pass < d.iterations ? ctx->denoise_pass : -1;
     d.stage = ctx->variance_stage;
     if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
-    RT_HIP_CHECK(launch_denoise_variance(d, s));
+    RT_HIP_CHECK(launch_filter(d, s));
     return ms ? elapsed_ms(p, s, ms) : RT_OK;
+}
+
+int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radiance, const rt_hit* d_hits,
+                      const rt_denoise_params* params, void* d_workspace, void* d_out_rgba, float* d_out_radiance,
+                      void* stream, double* ms) {
+    return denoise_device("rt_denoise_device", kFilterRadiance, ctx, width, height, d_radiance, nullptr, d_hits, params,
+                          nullptr, d_workspace, d_out_rgba, d_out_radiance, stream, ms);
+}
+
+int rt_denoise_history_device(rt_ctx* ctx, int width, int height, const void* d_hist, const rt_hit* d_hits,
+                              const rt_denoise_params* params, void* d_workspace, void* d_out_rgba,
+                              float* d_out_radiance, void* stream, double* ms) {
+    return denoise_device("rt_denoise_history_device", kFilterHistory, ctx, width, height, d_hist, nullptr, d_hits, params,
+                          nullptr, d_workspace, d_out_rgba, d_out_radiance, stream, ms);
+}
+
+int rt_denoise_variance_device(rt_ctx* ctx, int width, int height, const void* d_hist, const void* d_mom,
+                               const rt_hit* d_hits, const rt_variance_params* params, void* d_workspace,
+                               void* d_out_rgba, float* d_out_radiance, void* stream, double* ms) {
+    return denoise_device("rt_denoise_variance_device", kFilterVariance, ctx, width, height, d_hist, d_mom, d_hits,
+                          nullptr, params, d_workspace, d_out_rgba, d_out_radiance, stream, ms);
 }
 
 int rt_render_denoised(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
@@ -2450,11 +2420,19 @@ static int temporal_device(const char* fn, bool moments, rt_ctx* ctx, int width,
                            const void* d_hist_prev, const rt_hit* d_hits_prev, const rt_temporal_params* params,
                            void* d_hist_out, void* d_out_rgba, float* d_out_radiance, void* stream, double* ms,
                            const void* d_mom_prev, void* d_mom_out) {
-    if (!ctx || !cam || !d_radiance || !d_hits || !d_hist_out || (moments && !d_mom_out)) {
-        set_error(moments ? "%s: null context, camera, input, d_hist_out or d_mom_out"
-                          : "%s: null context, camera, input or d_hist_out", fn);
-        return RT_ERR_INVALID_ARG;
-    }
+    const char* const what_null = moments ? "context, camera, input, d_hist_out or d_mom_out"
+                                          : "context, camera, input or d_hist_out";
+    if (!ctx || !cam) { set_error("%s: null %s", fn, what_null); return RT_ERR_INVALID_ARG; }
+    const size_t px = rt_denoise_workspace_bytes(width, height) / 32;
+    const Buf bufs[9] = {{d_radiance, px * 12, 4, "d_radiance", kBufIn, false},
+                         {d_hits, px * 32, 16, "d_hits", kBufIn, false},
+                         {d_hist_prev, px * 16, 16, "d_hist_prev", kBufIn, true},
+                         {d_hits_prev, px * 32, 16, "d_hits_prev", kBufIn, true},
+                         {d_mom_prev, px * 8, 8, "d_mom_prev", kBufIn, true},
+                         {d_hist_out, px * 16, 16, "d_hist_out", kBufOut, false},
+                         {d_out_rgba, px * 4, 4, "d_out_rgba", kBufOut, true},
+                         {d_out_radiance, px * 12, 4, "d_out_radiance", kBufOut, true},
+                         {d_mom_out, px * 8, 8, "d_mom_out", kBufOut, !moments}};
     const int n_prev = (prev_cam != nullptr) + (d_hist_prev != nullptr) + (d_hits_prev != nullptr) +
                        (d_mom_prev != nullptr);
     if (n_prev != 0 && n_prev != (moments ? 4 : 3)) {
@@ -2462,7 +2440,7 @@ static int temporal_device(const char* fn, bool moments, rt_ctx* ctx, int width,
                           : "%s: prev_cam, d_hist_prev and d_hits_prev must be all null or all given", fn);
         return RT_ERR_INVALID_ARG;
     }
-    if (rt_denoise_workspace_bytes(width, height) == 0) {
+    if (px == 0) {
         set_error("%s: bad frame size %dx%d", fn, width, height);
         return RT_ERR_INVALID_ARG;
     }
@@ -2470,35 +2448,7 @@ static int temporal_device(const char* fn, bool moments, rt_ctx* ctx, int width,
     rt_temporal_default_params(&q);
     if (params) q = *params;
     if (int rc = check_temporal_params(&q, fn)) return rc;
-    if ((((uintptr_t)d_hits | (uintptr_t)d_hits_prev | (uintptr_t)d_hist_prev | (uintptr_t)d_hist_out) & 15u) ||
-        (((uintptr_t)d_radiance | (uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
-        set_error("%s: the hit and history buffers must be 16-byte aligned, the other buffers 4-byte", fn);
-        return RT_ERR_INVALID_ARG;
-    }
-    if (((uintptr_t)d_mom_prev | (uintptr_t)d_mom_out) & 7u) {
-        set_error("%s: the moments buffers must be 8-byte aligned", fn);
-        return RT_ERR_INVALID_ARG;
-    }
-    const size_t px = (size_t)width * (size_t)height;
-    struct Range { const void* p; size_t n; const char* name; };
-    const Range in[5] = {{d_radiance, px * 12, "d_radiance"}, {d_hits, px * 32, "d_hits"},
-                         {d_hist_prev, px * 16, "d_hist_prev"}, {d_hits_prev, px * 32, "d_hits_prev"},
-                         {d_mom_prev, px * 8, "d_mom_prev"}};
-    const Range out[4] = {{d_hist_out, px * 16, "d_hist_out"}, {d_out_rgba, px * 4, "d_out_rgba"},
-                          {d_out_radiance, px * 12, "d_out_radiance"}, {d_mom_out, px * 8, "d_mom_out"}};
-    for (int o = 0; o < 4; ++o) {
-        if (!out[o].p) continue;
-        for (const Range& i : in)
-            if (i.p && ranges_overlap(out[o].p, out[o].n, i.p, i.n)) {
-                set_error("%s: %s overlaps %s", fn, out[o].name, i.name);
-                return RT_ERR_INVALID_ARG;
-            }
-        for (int o2 = 0; o2 < o; ++o2)
-            if (out[o2].p && ranges_overlap(out[o].p, out[o].n, out[o2].p, out[o2].n)) {
-                set_error("%s: %s overlaps %s", fn, out[o].name, out[o2].name);
-                return RT_ERR_INVALID_ARG;
-            }
-    }
+    if (int rc = check_buffers(fn, what_null, bufs, 9)) return rc;
     PerDevice& p = ctx->dev[0];
     RT_HIP_CHECK(hipSetDevice(p.device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2517,10 +2467,10 @@ static int temporal_device(const char* fn, bool moments, rt_ctx* ctx, int width,
     t.out_rgba = static_cast<uchar4*>(d_out_rgba);
     t.out_rad = d_out_radiance;
     t.form = ctx->temporal_tile;
+    t.mom_prev = static_cast<const float2*>(d_mom_prev);
+    t.mom_out = static_cast<float2*>(d_mom_out);
     if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
-    RT_HIP_CHECK(moments ? launch_temporal_moments(t, static_cast<const float2*>(d_mom_prev),
-                                                   static_cast<float2*>(d_mom_out), s)
-                         : launch_temporal(t, s));
+    RT_HIP_CHECK(launch_temporal(t, s));
     return ms ? elapsed_ms(p, s, ms) : RT_OK;
 }
 
@@ -2810,20 +2760,13 @@ int rt_render_samples_device(rt_ctx* ctx, const rt_camera_ubo* cam, int width, i
         set_error("%s: a workspace of %zu bytes cannot hold one frame (%zu bytes)", fn, workspace_bytes, frame_bytes);
         return RT_ERR_INVALID_ARG;
     }
-    if ((((uintptr_t)d_workspace | (uintptr_t)d_sum) & 15u) || (((uintptr_t)d_out_rgba | (uintptr_t)d_out_radiance) & 3u)) {
-        set_error("%s: d_workspace and d_sum must be 16-byte aligned, the outputs 4-byte", fn);
-        return RT_ERR_INVALID_ARG;
-    }
     const int frames_ws = (int)std::min<size_t>((size_t)kMaxBatch, workspace_bytes / frame_bytes);
-    const struct { const void* p; size_t n; const char* name; } buf[4] = {
-        {d_workspace, (size_t)frames_ws * frame_bytes, "d_workspace"}, {d_sum, frame_bytes, "d_sum"},
-        {d_out_rgba, px * 4, "d_out_rgba"}, {d_out_radiance, frame_bytes, "d_out_radiance"}};
-    for (int i = 0; i < 4; ++i)
-        for (int j = i + 1; j < 4; ++j)
-            if (buf[i].p && buf[j].p && ranges_overlap(buf[i].p, buf[i].n, buf[j].p, buf[j].n)) {
-                set_error("%s: %s overlaps %s", fn, buf[j].name, buf[i].name);
-                return RT_ERR_INVALID_ARG;
-            }
+    // (the running sum is read and written: like an output, it may lie on nothing else)
+    const Buf bufs[4] = {{d_workspace, (size_t)frames_ws * frame_bytes, 16, "d_workspace", kBufWorkspace, false},
+                         {d_sum, frame_bytes, 16, "d_sum", kBufOut, false},
+                         {d_out_rgba, px * 4, 4, "d_out_rgba", kBufOut, true},
+                         {d_out_radiance, frame_bytes, 4, "d_out_radiance", kBufOut, true}};
+    if (int rc = check_buffers(fn, "buffer", bufs, 4)) return rc;
     PerDevice& p = ctx->dev[0];
     RT_HIP_CHECK(hipSetDevice(p.device));
     hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the null stream

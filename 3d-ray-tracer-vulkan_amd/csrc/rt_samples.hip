@@ -22,15 +22,10 @@
 //   scalar : a lane folds one pixel with 4-byte accesses; any size (slice f of
 //            a frame of 2553 floats starts 12 * f bytes off the grid)
 #include "rt_internal.h"
-
-#include <cmath>
+#include "rt_pixel.h"
 
 namespace rtamd {
 namespace {
-
-__device__ __forceinline__ uint8_t unorm8(float c) {   // the render's store (rt_trace.hip)
-    return c > 0.0f ? (c < 1.0f ? (uint8_t)__builtin_rintf(c * 255.0f) : (uint8_t)255) : (uint8_t)0;
-}
 
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 div4(float4 a, float d) { return make_float4(a.x / d, a.y / d, a.z / d, a.w / d); }

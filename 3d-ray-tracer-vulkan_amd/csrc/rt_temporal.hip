@@ -1,16 +1,23 @@
 // rt_temporal.hip — temporal accumulation reprojected through the first-hit
 // buffer (rtamd.h "temporal").
 //
-// One kernel.  A pixel with a hit projects its world position through the
-// current and the previous camera, follows the difference to where the surface
-// was in the previous frame, gathers the up to four history records around
-// that point whose own first hits lie on the same plane with the same normal,
-// and blends the new sample into their bilinear mean with weight 1 / n.  A
-// pixel without a hit, or one whose history is rejected, starts again from its
-// own sample.  All arithmetic is IEEE binary32 in the order DESIGN.md §4h
+// One kernel template.  A pixel with a hit projects its world position through
+// the current and the previous camera, follows the difference to where the
+// surface was in the previous frame, gathers the up to four history records
+// around that point whose own first hits lie on the same plane with the same
+// normal, and blends the new sample into their bilinear mean with weight 1 / n.
+// A pixel without a hit, or one whose history is rejected, starts again from
+// its own sample.  All arithmetic is IEEE binary32 in the order DESIGN.md §4h
 // writes it (the library is built with -ffp-contract=off, `/` and sqrtf are
 // correctly rounded, fminf drops a NaN operand), so tests/temporal_ref.py
 // restates it bit for bit.
+//
+// With MOMENTS (rt_temporal_moments_device) a second history
+// buffer travels beside the first: (m1, m2), the accumulated means of the
+// samples' luminance and of its square, gathered through the same taps with the
+// same weights.  The colour's operations are the same in the same order: the
+// same history, radiance and RGBA8 bits.  A tap costs 8 B more, a pixel writes
+// 8 B more.
 //
 // A memory-bound gather: a pixel reads its own 12 + 32 B, each tap 48 B (the
 // two 16-B halves of the previous hit record and one 16-B history record), and
@@ -21,19 +28,10 @@
 //   tiles : a wave on a 16 x 4 tile (the render's wave tile on the accel tree)
 // Which one ships was measured (kShippedForm below).
 #include "rt_internal.h"
-
-#include <cmath>
+#include "rt_pixel.h"
 
 namespace rtamd {
 namespace {
-
-__device__ __forceinline__ uint8_t unorm8(float c) {   // the render's store (rt_trace.hip)
-    return c > 0.0f ? (c < 1.0f ? (uint8_t)__builtin_rintf(c * 255.0f) : (uint8_t)255) : (uint8_t)0;
-}
-
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-    return (ax * bx + ay * by) + az * bz;
-}
 
 // project(C, P) of DESIGN.md §4h: the viewport coordinates whose ray from C's origin passes through P
 __device__ __forceinline__ bool project(const TemporalBasis& c, float px, float py, float pz, float& u, float& v) {
@@ -44,7 +42,7 @@ __device__ __forceinline__ bool project(const TemporalBasis& c, float px, float 
     return dn * c.det > 0.0f;
 }
 
-template <bool TILES>
+template <bool TILES, bool MOMENTS>
 __global__ __launch_bounds__(256) void temporal_kernel(TemporalArgs a, int tiles_x) {
     const int bx = (int)(blockIdx.x % (unsigned)tiles_x), by = (int)(blockIdx.x / (unsigned)tiles_x);
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -56,8 +54,10 @@ __global__ __launch_bounds__(256) void temporal_kernel(TemporalArgs a, int tiles
     const float4 p0 = a.hits[2 * p], p1 = a.hits[2 * p + 1];      // (t, tri, n.xy), (n.z, pos.xyz)
     const float gr = a.radiance[3 * p + 0], gg = a.radiance[3 * p + 1], gb = a.radiance[3 * p + 2];
     const float cr = gr * gr, cg = gg * gg, cb = gb * gb;
+    const float l = lum_of(cr, cg, cb), l2 = l * l;              // (MOMENTS alone reads them)
     const bool hit = __float_as_int(p0.y) >= 0;
     float orr = cr, og = cg, ob = cb, on = hit ? 1.0f : 0.0f;      // sky / invalid: passes through with n = 0
+    float o1 = l, o2 = l2;
     if (hit && a.hist_prev) {
         const float nx = p0.z, ny = p0.w, nz = p1.x, qx = p1.y, qy = p1.z, qz = p1.w;
         float uc, vc, up, vp;
@@ -71,6 +71,7 @@ __global__ __launch_bounds__(256) void temporal_kernel(TemporalArgs a, int tiles
             const int ix = (int)x0, iy = (int)y0;
             // the four taps' loads first, from addresses inside the frame either way
             float4 h0[4], h1[4], hc[4];
+            float2 hm[4];
             bool inside[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -80,8 +81,9 @@ __global__ __launch_bounds__(256) void temporal_kernel(TemporalArgs a, int tiles
                 h0[k] = a.hits_prev[2 * q];
                 h1[k] = a.hits_prev[2 * q + 1];
                 hc[k] = a.hist_prev[q];
+                if constexpr (MOMENTS) hm[k] = a.mom_prev[q];
             }
-            float sr = 0.0f, sg = 0.0f, sb = 0.0f, ws = 0.0f, nm = __builtin_inff();
+            float sr = 0.0f, sg = 0.0f, sb = 0.0f, ws = 0.0f, nm = __builtin_inff(), s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {                       // j outer, i inner
                 const float wt = ((k & 1) ? ax : 1.0f - ax) * ((k >> 1) ? ay : 1.0f - ay);
@@ -94,6 +96,10 @@ __global__ __launch_bounds__(256) void temporal_kernel(TemporalArgs a, int tiles
                 sb = take ? sb + wt * hc[k].z : sb;
                 ws = take ? ws + wt : ws;
                 nm = take ? __builtin_fminf(nm, hc[k].w) : nm;
+                if constexpr (MOMENTS) {
+                    s1 = take ? s1 + wt * hm[k].x : s1;
+                    s2 = take ? s2 + wt * hm[k].y : s2;
+                }
             }
             if (ws > 0.0f) {
                 const float hr = sr / ws, hg = sg / ws, hb = sb / ws;
@@ -102,10 +108,18 @@ __global__ __launch_bounds__(256) void temporal_kernel(TemporalArgs a, int tiles
                 og = hg + (cg - hg) * inv;
                 ob = hb + (cb - hb) * inv;
                 on = nn;
+                if constexpr (MOMENTS) {
+                    const float h1m = s1 / ws, h2m = s2 / ws;
+                    o1 = h1m + (l - h1m) * inv;
+                    o2 = h2m + (l2 - h2m) * inv;
+                }
             }
         }
     }
     a.hist_out[p] = make_float4(orr, og, ob, on);
+    if constexpr (MOMENTS) a.mom_out[p] = make_float2(o1, o2);
+    // rt_pixel.h's store_display, written out: through the call the compiler no longer shares 3 * p between
+    // the radiance loads above and these stores, and the kernel's registers and instructions change
     if (a.out_rgba || a.out_rad) {
         const float rr = sqrtf(orr), rg = sqrtf(og), rb = sqrtf(ob);
         if (a.out_rgba) a.out_rgba[p] = make_uchar4(unorm8(rr), unorm8(rg), unorm8(rb), 255);
@@ -127,11 +141,10 @@ constexpr int kShippedForm = 1;
 
 hipError_t launch_temporal(const TemporalArgs& t, hipStream_t stream) {
     const size_t tx = ((size_t)t.width + 63) / 64, ty = ((size_t)t.height + 3) / 4;   // <= 2^29 workgroups
-    const int form = t.form ? t.form : kShippedForm;
-    if (form == 2)
-        hipLaunchKernelGGL(temporal_kernel<true>, dim3((unsigned)(tx * ty)), dim3(256), 0, stream, t, (int)tx);
-    else
-        hipLaunchKernelGGL(temporal_kernel<false>, dim3((unsigned)(tx * ty)), dim3(256), 0, stream, t, (int)tx);
+    const bool tiles = (t.form ? t.form : kShippedForm) == 2;
+    const auto kernel = t.mom_out ? (tiles ? temporal_kernel<true, true> : temporal_kernel<false, true>)
+                                  : (tiles ? temporal_kernel<true, false> : temporal_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(tx * ty)), dim3(256), 0, stream, t, (int)tx);
     return hipGetLastError();
 }
 

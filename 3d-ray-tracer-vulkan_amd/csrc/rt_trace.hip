@@ -40,6 +40,7 @@
 #include <cstring>
 
 #include "rt_internal.h"
+#include "rt_pixel.h"
 
 namespace rtamd {
 
@@ -87,11 +88,6 @@ __device__ __forceinline__ V3 rnd_in_sphere(uint32_t& seed) {
         if (vdot(p, p) < 1.0f) return p;
     }
     return {0.0f, 0.0f, 0.0f};
-}
-
-__device__ __forceinline__ uint8_t unorm8(float c) {
-    // VkFormat R8G8B8A8_UNORM store: clamp to [0,1], round to nearest even.
-    return c > 0.0f ? (c < 1.0f ? (uint8_t)__builtin_rintf(c * 255.0f) : (uint8_t)255) : (uint8_t)0;
 }
 
 // Frame row of local row ly of frame f of the launch (rt_internal.h, TraceArgs

@@ -52,8 +52,8 @@ EXPORTED = (
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
 # "src=" field is the first 16 hex digits of SHA-256 over them concatenated.
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
-                 "csrc/rt_denoise.hip", "csrc/rt_denoise_history.hip", "csrc/rt_temporal.hip", "csrc/rt_variance.hip",
-                 "csrc/rt_samples.hip", "csrc/rt_refit.hip", "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h",
+                 "csrc/rt_filter.hip", "csrc/rt_temporal.hip", "csrc/rt_samples.hip", "csrc/rt_refit.hip",
+                 "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h", "csrc/rt_pixel.h",
                  "csrc/accel_build.h", "../include/rtamd.h")
 
 

@@ -162,6 +162,42 @@ def test_single_outputs(r, synthetic, form):
     assert none is None and np.array_equal(out.view(np.uint32), want_rad.view(np.uint32))
 
 
+@pytest.mark.parametrize("form", [1, 2])
+def test_lone_passes_on_one_workspace(r, rendered, form):
+    """Option denoise_pass: passes 0, 1 and 2 of a 3-pass filter, each enqueued
+    alone on one workspace (steps 1, 2 and 4; at 37x23 a step-4 residue class
+    ends inside the first tile), leave what the whole filter leaves; a pass
+    that is not the last writes neither output."""
+    import torch
+    import rtamd
+    rad, hits = rendered[(37, 23)]
+    h, w = rad.shape[:2]
+    rad, hits = np.ascontiguousarray(rad, np.float32), np.ascontiguousarray(hits)
+    kw = {**D.DEFAULTS, "iterations": 3}
+    params = rtamd.DenoiseParams(**kw)
+    want_rad, want_rgba = D.denoise(rad, hits, **kw)
+    whole_rgba, whole_rad = run(r, rad, hits, params, form)
+    d_rad, d_hit = Guarded(w * h * 12, rad), Guarded(w * h * 32, hits)
+    d_ws, o_rgba, o_rad = Guarded(r.denoise_workspace_bytes(w, h)), Guarded(w * h * 4), Guarded(w * h * 12)
+    r.set_option("denoise_kernel", form)
+    try:
+        for i in range(3):
+            r.set_option("denoise_pass", i)
+            r.denoise_device(w, h, d_rad.ptr, d_hit.ptr, d_ws.ptr, o_rgba.ptr, o_rad.ptr, params,
+                             torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            if i < 2:
+                assert (o_rgba.host(np.uint8, -1) == 0xEE).all() and (o_rad.host(np.uint8, -1) == 0xEE).all(), i
+    finally:
+        r.set_option("denoise_pass", -1)
+        r.set_option("denoise_kernel", 0)
+    for b in (d_rad, d_hit, d_ws, o_rgba, o_rad):
+        assert b.guards_intact()
+    rgba, out = o_rgba.host(np.uint8, (h, w, 4)), o_rad.host(np.float32, (h, w, 3))
+    assert np.array_equal(out.view(np.uint32), whole_rad.view(np.uint32)) and np.array_equal(rgba, whole_rgba)
+    assert np.array_equal(out.view(np.uint32), want_rad.view(np.uint32)) and np.array_equal(rgba, want_rgba)
+
+
 def test_host_array_form(r, rendered):
     rad, hits = rendered[(37, 23)]
     want_rad, want_rgba = D.denoise(rad, hits)

@@ -425,6 +425,44 @@ def test_the_estimate_alone_writes_no_output(r, frames):
     assert np.array_equal(bits(rec), bits(V.estimate(hist, mom, hits)))
 
 
+@pytest.mark.parametrize("form", [1, 2])
+def test_lone_passes_on_one_workspace(r, frames, form):
+    """Option denoise_pass: the estimate alone (option variance_stage 0: a lone
+    pass skips it), then passes 0, 1 and 2 of a 3-pass filter, each enqueued alone
+    on one workspace (steps 1, 2 and 4), leave what the whole filter leaves; a
+    pass that is not the last writes neither output."""
+    import torch
+    import rtamd
+    hist, mom, hits = frames[(37, 23)]
+    h, w = hist.shape[:2]
+    hist, mom, hits = np.ascontiguousarray(hist, F), np.ascontiguousarray(mom, F), np.ascontiguousarray(hits)
+    kw = {**V.DEFAULTS, "iterations": 3}
+    params = rtamd.VarianceParams(**kw)
+    want_rad, want_rgba = V.denoise_variance(hist, mom, hits, **kw)
+    whole_rgba, whole_rad = run(r, hist, mom, hits, params, form)
+    d_hist, d_mom, d_hit = Guarded(w * h * 16, hist), Guarded(w * h * 8, mom), Guarded(w * h * 32, hits)
+    d_ws, o_rgba, o_rad = Guarded(r.denoise_workspace_bytes(w, h)), Guarded(w * h * 4), Guarded(w * h * 12)
+    r.set_option("denoise_kernel", form)
+    try:
+        for i in (-1, 0, 1, 2):                     # -1: the estimate
+            r.set_option("variance_stage", 0 if i < 0 else -1)
+            r.set_option("denoise_pass", i)
+            r.denoise_variance_device(w, h, d_hist.ptr, d_mom.ptr, d_hit.ptr, d_ws.ptr, o_rgba.ptr, o_rad.ptr, params,
+                                      torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            if i < 2:
+                assert (o_rgba.host(np.uint8, -1) == 0xEE).all() and (o_rad.host(np.uint8, -1) == 0xEE).all(), i
+    finally:
+        r.set_option("variance_stage", -1)
+        r.set_option("denoise_pass", -1)
+        r.set_option("denoise_kernel", 0)
+    for b in (d_hist, d_mom, d_hit, d_ws, o_rgba, o_rad):
+        assert b.guards_intact()
+    rgba, out = o_rgba.host(np.uint8, (h, w, 4)), o_rad.host(np.float32, (h, w, 3))
+    assert np.array_equal(bits(out), bits(whole_rad)) and np.array_equal(rgba, whole_rgba)
+    assert np.array_equal(bits(out), bits(want_rad)) and np.array_equal(rgba, want_rgba)
+
+
 # ---- rt_render_temporal_variance ----------------------------------------------------
 
 def composed_frame(rr, w, h, cam, prev, tp, vp):
