@@ -350,7 +350,16 @@ struct TemporalArgs {
     const float2* mom_prev;
     float2*       mom_out;
 };
-hipError_t launch_temporal(const TemporalArgs& t, hipStream_t stream);
+// rt_temporal_motion_device: the vertex records, 3 float4 per flattened triangle, as the
+// frame's hit records saw them and as the previous frame's did.  A kernel argument of its own behind the
+// others, so that the kernels without it keep their argument layout.
+struct TemporalMotion {
+    const float4* verts_cur = nullptr;
+    const float4* verts_prev = nullptr;
+    unsigned      n_tris = 0;       // 1..2^29: a hit record whose tri is not below it has no history
+};
+// motion null: the kernels of §4h and §4j
+hipError_t launch_temporal(const TemporalArgs& t, hipStream_t stream, const TemporalMotion* motion = nullptr);
 
 // rt_samples.hip: folds the linear-colour frames of one samples launch into
 // the running sum, in frame order (rtamd.h rt_render_samples_device, DESIGN.md

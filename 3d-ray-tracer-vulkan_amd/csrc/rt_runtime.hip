@@ -4,6 +4,7 @@
 // barriers, staging image) has no counterpart: device buffers + one HIP
 // stream per device.
 #include "rt_internal.h"
+#include "temporal_motion_host.h"
 
 #include "accel_build.h"
 
@@ -349,6 +350,13 @@ struct PerDevice {
     char*        d_refit = nullptr;
     size_t       refit_bytes = 0;
     RefitTables  refit;
+    // option temporal_motion: the bookkeeping (temporal_motion_host.h) of refit.st_verts,
+    // which holds the scene's current vertex records once staged, and of d_verts_prev (48 B per flattened
+    // triangle, allocated at the first update of a scene that keeps the history), which holds them as the
+    // last temporal frame's hit buffer saw them while an update is pending
+    MotionBook   motion;
+    char*        d_verts_prev = nullptr;
+    int          motion_used = 0;    // the last rt_render_temporal* call ran the MOTION kernel
 };
 
 static constexpr size_t kMaxOrders = 16;
@@ -501,6 +509,8 @@ struct rt_ctx {
                                    //   per wave, walked cooperatively, in a separate launch
                                    //   (-1 = automatic: the tiles that outlast the bulk, learn_order)
     int  refit = 0;                // at the next upload: keep what rt_update_geometry needs
+    int  temporal_motion = 0;      // rt_update_geometry keeps rt_render_temporal's history and the next temporal
+                                   //   frame reprojects it per triangle
     // The host side of those tables: the uploaded buffers' sizes, every node's 24 bytes outside its boxes
     // (offsets 12-15 and 28-47), the duplicates the accel build dropped (AccelHost::dup_pairs) and where
     // each height's nodes start in RefitTables::by_height.  refit_held: the current scene has them.
@@ -530,6 +540,9 @@ static void free_scene(PerDevice& p) {
     p.d_refit = nullptr;
     p.refit_bytes = 0;
     p.refit = RefitTables{};
+    if (p.d_verts_prev) (void)hipFree(p.d_verts_prev);
+    p.d_verts_prev = nullptr;
+    p.motion = MotionBook{};
     p.scene = DevScene{};
 }
 
@@ -1591,6 +1604,12 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
             e = hipMalloc(&p.d_refit, p.refit_bytes ? p.refit_bytes : 16);
             if (e == hipSuccess && !rtab.empty())
                 e = hipMemcpy(p.d_refit + st_bytes, rtab.data(), rtab.size(), hipMemcpyHostToDevice);
+            // Option temporal_motion: the state before the first update is the uploaded records, copied from
+            // the caller's buffer into the staging array an update would fill (no memory of its own).
+            if (e == hipSuccess && ctx->temporal_motion && ctx->dev.size() == 1 && hs.n_tris) {
+                e = hipMemcpy(p.d_refit, vertices, (size_t)hs.n_tris * 48, hipMemcpyHostToDevice);
+                p.motion.on_upload(e == hipSuccess);
+            }
             RefitTables& t = p.refit;
             char* tb = p.d_refit + st_bytes;
             t.st_verts = reinterpret_cast<const float4*>(p.d_refit);
@@ -1697,7 +1716,27 @@ int rt_update_geometry(rt_ctx* ctx, const void* vertices, size_t vertex_bytes, c
     for (PerDevice& p : ctx->dev) {
         RT_HIP_CHECK(hipSetDevice(p.device));
         RT_HIP_CHECK(hipDeviceSynchronize());            // frames in flight read the records rewritten below
-        p.temporal_valid = false;                        // rt_render_temporal starts a new sequence
+        // Option temporal_motion: the history stays, and the records the last temporal frame
+        // saw are kept beside it, copied at the first update since that frame only.
+        bool copy = false;
+        const bool keep = p.motion.on_update(ctx->temporal_motion != 0, ctx->dev.size(), p.temporal_valid, n_tris, n_nodes,
+                                             &copy);
+        if (copy) {
+            if (!p.d_verts_prev) {
+                const hipError_t e = hipMalloc(&p.d_verts_prev, 48 * n_tris);
+                if (e != hipSuccess) {
+                    p.d_verts_prev = nullptr;
+                    p.motion.on_history_dropped();
+                    p.temporal_valid = false;
+                    set_error("rt_update_geometry: %zu bytes for the previous vertex records: %s", 48 * n_tris,
+                              hipGetErrorString(e));
+                    return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+                }
+            }
+            RT_HIP_CHECK(hipMemcpyAsync(p.d_verts_prev, p.refit.st_verts, 48 * n_tris, hipMemcpyDeviceToDevice,
+                                        p.stream));
+        }
+        if (!keep) p.temporal_valid = false;             // rt_render_temporal starts a new sequence
         p.samples_held = 0;                              // and rt_render_samples a new sum
         if (n_nodes == 0) continue;                      // an empty scene stays empty
         if (n_tris)
@@ -1719,6 +1758,7 @@ int rt_update_geometry(rt_ctx* ctx, const void* vertices, size_t vertex_bytes, c
             *ms = t;
         }
         std::memcpy(p.scene.root_box, boxes.data(), sizeof p.scene.root_box);
+        p.motion.after_update(n_tris);                   // the staging array now holds the scene's records
     }
     return RT_OK;
 }
@@ -1782,7 +1822,10 @@ int rt_upload_spheres(rt_ctx* ctx, const float* spheres, int n_spheres) {
         p.n_spheres = n_spheres;
     }
     ++ctx->scene_gen;    // learned tile orders see the new work
-    for (PerDevice& p : ctx->dev) p.temporal_valid = false;   // rt_render_temporal starts a new sequence
+    for (PerDevice& p : ctx->dev) {                           // rt_render_temporal starts a new sequence
+        p.temporal_valid = false;
+        p.motion.on_history_dropped();
+    }
     for (PerDevice& p : ctx->dev) p.samples_held = 0;         // and rt_render_samples a new sum
     return RT_OK;
 }
@@ -2419,12 +2462,21 @@ static int temporal_device(const char* fn, bool moments, rt_ctx* ctx, int width,
                            const float* d_radiance, const rt_hit* d_hits, const rt_camera_ubo* prev_cam,
                            const void* d_hist_prev, const rt_hit* d_hits_prev, const rt_temporal_params* params,
                            void* d_hist_out, void* d_out_rgba, float* d_out_radiance, void* stream, double* ms,
-                           const void* d_mom_prev, void* d_mom_out) {
+                           const void* d_mom_prev, void* d_mom_out, const void* d_verts_cur = nullptr,
+                           const void* d_verts_prev = nullptr, size_t n_tris = 0) {
     const char* const what_null = moments ? "context, camera, input, d_hist_out or d_mom_out"
                                           : "context, camera, input or d_hist_out";
     if (!ctx || !cam) { set_error("%s: null %s", fn, what_null); return RT_ERR_INVALID_ARG; }
     const size_t px = rt_denoise_workspace_bytes(width, height) / 32;
-    const Buf bufs[9] = {{d_radiance, px * 12, 4, "d_radiance", kBufIn, false},
+    const bool motion = d_verts_cur || d_verts_prev;
+    if (const char* why = temporal_motion_args_error(d_verts_cur, d_verts_prev, prev_cam != nullptr, n_tris)) {
+        set_error(why, fn);
+        return RT_ERR_INVALID_ARG;
+    }
+    const size_t vbytes = motion ? n_tris * RT_VERTEX_RECORD_BYTES : 0;
+    const Buf bufs[11] = {{d_verts_cur, vbytes, 16, "d_verts_cur", kBufIn, true},
+                         {d_verts_prev, vbytes, 16, "d_verts_prev", kBufIn, true},
+                         {d_radiance, px * 12, 4, "d_radiance", kBufIn, false},
                          {d_hits, px * 32, 16, "d_hits", kBufIn, false},
                          {d_hist_prev, px * 16, 16, "d_hist_prev", kBufIn, true},
                          {d_hits_prev, px * 32, 16, "d_hits_prev", kBufIn, true},
@@ -2448,7 +2500,7 @@ static int temporal_device(const char* fn, bool moments, rt_ctx* ctx, int width,
     rt_temporal_default_params(&q);
     if (params) q = *params;
     if (int rc = check_temporal_params(&q, fn)) return rc;
-    if (int rc = check_buffers(fn, what_null, bufs, 9)) return rc;
+    if (int rc = check_buffers(fn, what_null, bufs, 11)) return rc;
     PerDevice& p = ctx->dev[0];
     RT_HIP_CHECK(hipSetDevice(p.device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2470,7 +2522,11 @@ static int temporal_device(const char* fn, bool moments, rt_ctx* ctx, int width,
     t.mom_prev = static_cast<const float2*>(d_mom_prev);
     t.mom_out = static_cast<float2*>(d_mom_out);
     if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
-    RT_HIP_CHECK(launch_temporal(t, s));
+    TemporalMotion mv;
+    mv.verts_cur = static_cast<const float4*>(d_verts_cur);
+    mv.verts_prev = static_cast<const float4*>(d_verts_prev);
+    mv.n_tris = (unsigned)n_tris;
+    RT_HIP_CHECK(launch_temporal(t, s, motion ? &mv : nullptr));
     return ms ? elapsed_ms(p, s, ms) : RT_OK;
 }
 
@@ -2491,6 +2547,17 @@ int rt_temporal_moments_device(rt_ctx* ctx, int width, int height, const rt_came
     return temporal_device("rt_temporal_moments_device", true, ctx, width, height, cam, d_radiance, d_hits, prev_cam,
                            d_hist_prev, d_hits_prev, params, d_hist_out, d_out_rgba, d_out_radiance, stream, ms,
                            d_mom_prev, d_mom_out);
+}
+
+int rt_temporal_motion_device(rt_ctx* ctx, int width, int height, const rt_camera_ubo* cam, const float* d_radiance,
+                              const rt_hit* d_hits, const rt_camera_ubo* prev_cam, const void* d_hist_prev,
+                              const rt_hit* d_hits_prev, const rt_temporal_params* params, void* d_hist_out,
+                              void* d_out_rgba, float* d_out_radiance, void* stream, double* ms,
+                              const void* d_mom_prev, void* d_mom_out, const void* d_verts_cur,
+                              const void* d_verts_prev, size_t n_tris) {
+    return temporal_device("rt_temporal_motion_device", d_mom_prev || d_mom_out, ctx, width, height, cam, d_radiance,
+                           d_hits, prev_cam, d_hist_prev, d_hits_prev, params, d_hist_out, d_out_rgba, d_out_radiance,
+                           stream, ms, d_mom_prev, d_mom_out, d_verts_cur, d_verts_prev, n_tris);
 }
 
 // rt_render_temporal (mode 0: dparams null = no filter, else rt_denoise_device on the temporal radiance),
@@ -2542,6 +2609,9 @@ static int render_temporal(const char* fn, int mode, rt_ctx* ctx, const rt_camer
     if ((flags & RT_TEMPORAL_RESET) || width != p.temporal_w || height != p.temporal_h) p.temporal_valid = false;
     // the moments are not those of the history (rt_render_temporal or _adaptive advanced it last): a new sequence
     if (variance && !p.moments_valid) p.temporal_valid = false;
+    // an update kept the history for the MOTION kernel: without the option it is of no use to §4h's
+    if (!p.motion.frame_keeps_history(ctx->temporal_motion != 0)) p.temporal_valid = false;
+    if (!p.temporal_valid) p.motion.on_history_dropped();
     if (total > p.temporal_cap) {
         char* grown = nullptr;
         const hipError_t e = hipMalloc(&grown, total);
@@ -2577,16 +2647,32 @@ static int render_temporal(const char* fn, int mode, rt_ctx* ctx, const rt_camer
     if (rc) return rc;
     const bool filter = adaptive || variance || dparams != nullptr;
     double t_ms = 0.0, dn_ms = 0.0;
+    // option temporal_motion: an update since the last frame, so the history is gathered per triangle
+    // (rt_temporal_motion_device) from the records that frame saw to the ones the refit staged
+    const bool motion = p.motion.take_frame(hist);
+    const void* const v_cur = motion ? p.refit.st_verts : nullptr;
+    const void* const v_prev = motion ? p.d_verts_prev : nullptr;
     p.temporal_valid = false;                    // (a failure below leaves no half-written history behind)
     p.moments_valid = false;
+    p.motion_used = motion ? 1 : 0;
     char* d_mom[2] = {nullptr, nullptr};         // (the variance-guided filter's alone)
     if (variance) {
         d_mom[0] = base + o_mom;
         d_mom[1] = base + o_mom + up(px * 8);
-        rc = rt_temporal_moments_device(ctx, width, height, cam, d_rad, d_hits[cur], hist ? &p.temporal_cam : nullptr,
-                                        hist ? d_hist[prev] : nullptr, hist ? d_hits[prev] : nullptr, tparams,
-                                        d_hist[cur], nullptr, nullptr, p.stream, stats ? &t_ms : nullptr,
-                                        hist ? d_mom[prev] : nullptr, d_mom[cur]);
+        rc = motion ? rt_temporal_motion_device(ctx, width, height, cam, d_rad, d_hits[cur], &p.temporal_cam,
+                                                d_hist[prev], d_hits[prev], tparams, d_hist[cur], nullptr, nullptr,
+                                                p.stream, stats ? &t_ms : nullptr, d_mom[prev], d_mom[cur], v_cur,
+                                                v_prev, (size_t)ctx->n_tris)
+                    : rt_temporal_moments_device(ctx, width, height, cam, d_rad, d_hits[cur],
+                                                 hist ? &p.temporal_cam : nullptr, hist ? d_hist[prev] : nullptr,
+                                                 hist ? d_hits[prev] : nullptr, tparams, d_hist[cur], nullptr, nullptr,
+                                                 p.stream, stats ? &t_ms : nullptr, hist ? d_mom[prev] : nullptr,
+                                                 d_mom[cur]);
+    } else if (motion) {
+        rc = rt_temporal_motion_device(ctx, width, height, cam, d_rad, d_hits[cur], &p.temporal_cam, d_hist[prev],
+                                       d_hits[prev], tparams, d_hist[cur], filter ? nullptr : base + o_rgba,
+                                       ((filter && !adaptive) || (!filter && out_radiance)) ? d_trad : nullptr, p.stream,
+                                       stats ? &t_ms : nullptr, nullptr, nullptr, v_cur, v_prev, (size_t)ctx->n_tris);
     } else {
         rc = rt_temporal_device(ctx, width, height, cam, d_rad, d_hits[cur], hist ? &p.temporal_cam : nullptr,
                                 hist ? d_hist[prev] : nullptr, hist ? d_hits[prev] : nullptr, tparams, d_hist[cur],
@@ -3263,6 +3349,7 @@ static const Option kOptions[] = {
     in_range("denoise_kernel", &rt_ctx::denoise_kernel, 0, 2),
     in_range("denoise_pass", &rt_ctx::denoise_pass, -1, 5),
     in_range("temporal_tile", &rt_ctx::temporal_tile, 0, 2),
+    one_of("temporal_motion", &rt_ctx::temporal_motion, 0, 1),
     in_range("variance_stage", &rt_ctx::variance_stage, -1, 0),
     in_range("sample_frames", &rt_ctx::sample_frames, 1, kMaxBatch),
     one_of("samples_kernel", &rt_ctx::samples_kernel, 0, 1),
@@ -3315,6 +3402,7 @@ int rt_get_option(rt_ctx* ctx, const char* name, int64_t* value) {
     else if (is("walk_bytes")) *value = p ? (int64_t)walk_bytes(*p) : 0;
     else if (is("refit_used")) *value = ctx->refit_held ? 1 : 0;
     else if (is("refit_bytes")) *value = p ? (int64_t)p->refit_bytes : 0;
+    else if (is("temporal_motion_used")) *value = p ? p->motion_used : 0;
     else if (is("leaf_align_used")) *value = p ? p->scene.padded : 0;
     else if (is("heavy_pixels_used")) *value = p ? p->last_heavy_px : 0;
     else if (is("heavy_tiles_used")) *value = p ? p->last_heavy : 0;

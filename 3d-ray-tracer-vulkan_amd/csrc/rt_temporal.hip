@@ -19,6 +19,17 @@
 // same history, radiance and RGBA8 bits.  A tap costs 8 B more, a pixel writes
 // 8 B more.
 //
+// With MOTION (rt_temporal_motion_device) the triangles may have
+// moved between the two frames: the pixel's triangle is read from the current
+// and from the previous vertex records, the hit point is expressed in the
+// barycentric coordinates of the one and evaluated on the other (binary64, in
+// §4m's order), and that point and the previous normal stand in for the
+// pixel's own on the previous-frame side: the projection through the previous
+// camera and the taps' two tests.  A triangle whose nine coordinates are the
+// same bits in both is the static contract exactly; a triangle index outside
+// the records or a result that is not finite starts the pixel over.  The
+// instantiations without MOTION do not read the extra kernel argument.
+//
 // A memory-bound gather: a pixel reads its own 12 + 32 B, each tap 48 B (the
 // two 16-B halves of the previous hit record and one 16-B history record), and
 // writes 16 + 12 + 4 B.  The four taps' twelve loads are issued together from
@@ -42,8 +53,46 @@ __device__ __forceinline__ bool project(const TemporalBasis& c, float px, float 
     return dn * c.det > 0.0f;
 }
 
-template <bool TILES, bool MOMENTS>
-__global__ __launch_bounds__(256) void temporal_kernel(TemporalArgs a, int tiles_x) {
+// §4m's dot and cross in binary64 (the library is built with -ffp-contract=off: one rounding per operation)
+__device__ __forceinline__ double dot3d(double ax, double ay, double az, double bx, double by, double bz) {
+    return (ax * bx + ay * by) + az * bz;
+}
+
+// The previous-frame side of a pixel across a geometry update (MOTION): its hit point q in the
+// barycentric coordinates of its triangle as the current record c holds it, evaluated on the previous record
+// v; the previous normal on the side the current one faces.  False when a component is not finite.
+__device__ __forceinline__ bool previous_point(const float4 (&c)[3], const float4 (&v)[3], float qx, float qy, float qz,
+                                               float nx, float ny, float nz, float (&P)[3], float (&N)[3]) {
+    const float e1x = c[1].x - c[0].x, e1y = c[1].y - c[0].y, e1z = c[1].z - c[0].z;
+    const float e2x = c[2].x - c[0].x, e2y = c[2].y - c[0].y, e2z = c[2].z - c[0].z;
+    const float f1x = v[1].x - v[0].x, f1y = v[1].y - v[0].y, f1z = v[1].z - v[0].z;
+    const float f2x = v[2].x - v[0].x, f2y = v[2].y - v[0].y, f2z = v[2].z - v[0].z;
+    const double wx = (double)qx - (double)c[0].x, wy = (double)qy - (double)c[0].y, wz = (double)qz - (double)c[0].z;
+    const double d11 = dot3d(e1x, e1y, e1z, e1x, e1y, e1z), d12 = dot3d(e1x, e1y, e1z, e2x, e2y, e2z),
+                 d22 = dot3d(e2x, e2y, e2z, e2x, e2y, e2z);
+    const double w1 = dot3d(wx, wy, wz, e1x, e1y, e1z), w2 = dot3d(wx, wy, wz, e2x, e2y, e2z);
+    const double den = d11 * d22 - d12 * d12;
+    const double b1 = (d22 * w1 - d12 * w2) / den, b2 = (d11 * w2 - d12 * w1) / den;
+    P[0] = (float)(((double)v[0].x + b1 * (double)f1x) + b2 * (double)f2x);
+    P[1] = (float)(((double)v[0].y + b1 * (double)f1y) + b2 * (double)f2y);
+    P[2] = (float)(((double)v[0].z + b1 * (double)f1z) + b2 * (double)f2z);
+    const double mx = (double)e1y * (double)e2z - (double)e1z * (double)e2y,
+                 my = (double)e1z * (double)e2x - (double)e1x * (double)e2z,
+                 mz = (double)e1x * (double)e2y - (double)e1y * (double)e2x;
+    const double px = (double)f1y * (double)f2z - (double)f1z * (double)f2y,
+                 py = (double)f1z * (double)f2x - (double)f1x * (double)f2z,
+                 pz = (double)f1x * (double)f2y - (double)f1y * (double)f2x;
+    const double s = dot3d(mx, my, mz, nx, ny, nz) < 0.0 ? -1.0 : 1.0;
+    const double len = __builtin_sqrt(dot3d(px, py, pz, px, py, pz));
+    N[0] = (float)((px / len) * s);
+    N[1] = (float)((py / len) * s);
+    N[2] = (float)((pz / len) * s);
+    const auto finite = [](float f) { return __builtin_fabsf(f) < __builtin_inff(); };      // (a NaN fails)
+    return finite(P[0]) && finite(P[1]) && finite(P[2]) && finite(N[0]) && finite(N[1]) && finite(N[2]);
+}
+
+template <bool TILES, bool MOMENTS, bool MOTION>
+__global__ __launch_bounds__(256) void temporal_kernel(TemporalArgs a, int tiles_x, TemporalMotion mv) {
     const int bx = (int)(blockIdx.x % (unsigned)tiles_x), by = (int)(blockIdx.x / (unsigned)tiles_x);
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const int x = bx * 64 + (TILES ? (int)(wave * 16u + (lane & 15u)) : (int)lane);
@@ -56,16 +105,46 @@ __global__ __launch_bounds__(256) void temporal_kernel(TemporalArgs a, int tiles
     const float cr = gr * gr, cg = gg * gg, cb = gb * gb;
     const float l = lum_of(cr, cg, cb), l2 = l * l;              // (MOMENTS alone reads them)
     const bool hit = __float_as_int(p0.y) >= 0;
+    // MOTION: the pixel's triangle in the current and the previous vertex records, from an index inside the
+    // buffers either way; lanes on one triangle share the six loads
+    float4 vc[3], vq[3];
+    bool known = true;                                           // tri < n_tris
+    if constexpr (MOTION) {
+        known = (unsigned)__float_as_int(p0.y) < mv.n_tris;
+        const size_t t3 = known ? 3 * (size_t)(unsigned)__float_as_int(p0.y) : 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            vc[k] = mv.verts_cur[t3 + k];
+            vq[k] = mv.verts_prev[t3 + k];
+        }
+    }
     float orr = cr, og = cg, ob = cb, on = hit ? 1.0f : 0.0f;      // sky / invalid: passes through with n = 0
     float o1 = l, o2 = l2;
     if (hit && a.hist_prev) {
-        const float nx = p0.z, ny = p0.w, nz = p1.x, qx = p1.y, qy = p1.z, qz = p1.w;
-        float uc, vc, up, vp;
-        const bool fc = project(a.cur, qx, qy, qz, uc, vc);
+        float nx = p0.z, ny = p0.w, nz = p1.x, qx = p1.y, qy = p1.z, qz = p1.w;
+        float uc, vc_, up, vp;
+        const bool fc = project(a.cur, qx, qy, qz, uc, vc_);
+        if constexpr (MOTION) {
+            // an unmoved triangle (the nine floats bit for bit) is §4h exactly: P' and n' are selected, the
+            // taps below are loaded by every lane alike
+            bool moved = false;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                moved = moved || __float_as_int(vc[k].x) != __float_as_int(vq[k].x) ||
+                        __float_as_int(vc[k].y) != __float_as_int(vq[k].y) ||
+                        __float_as_int(vc[k].z) != __float_as_int(vq[k].z);
+            if (moved) {
+                float P[3], N[3];
+                const bool fin = previous_point(vc, vq, qx, qy, qz, nx, ny, nz, P, N);
+                known = known && fin;
+                qx = P[0]; qy = P[1]; qz = P[2];
+                nx = N[0]; ny = N[1]; nz = N[2];
+            }
+        }
         const bool fp = project(a.prev, qx, qy, qz, up, vp);
         const float fW = (float)W, fH = (float)H;
-        const float fx = (float)x + (up - uc) * fW, fy = (float)y + (vc - vp) * fH;
-        if (fc && fp && fx > -1.0f && fx < fW && fy > -1.0f && fy < fH) {      // (a NaN fails)
+        const float fx = (float)x + (up - uc) * fW, fy = (float)y + (vc_ - vp) * fH;
+        if (known && fc && fp && fx > -1.0f && fx < fW && fy > -1.0f && fy < fH) {      // (a NaN fails)
             const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
             const float ax = fx - x0, ay = fy - y0, tol = a.plane_tol * p0.x;
             const int ix = (int)x0, iy = (int)y0;
@@ -139,12 +218,17 @@ constexpr int kShippedForm = 1;
 
 }  // namespace
 
-hipError_t launch_temporal(const TemporalArgs& t, hipStream_t stream) {
+hipError_t launch_temporal(const TemporalArgs& t, hipStream_t stream, const TemporalMotion* motion) {
     const size_t tx = ((size_t)t.width + 63) / 64, ty = ((size_t)t.height + 3) / 4;   // <= 2^29 workgroups
     const bool tiles = (t.form ? t.form : kShippedForm) == 2;
-    const auto kernel = t.mom_out ? (tiles ? temporal_kernel<true, true> : temporal_kernel<false, true>)
-                                  : (tiles ? temporal_kernel<true, false> : temporal_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(tx * ty)), dim3(256), 0, stream, t, (int)tx);
+    // MOTION only with vertex buffers (rt_temporal_motion_device): without them the kernels of §4h and §4j
+    const auto kernel =
+        motion ? (t.mom_out ? (tiles ? temporal_kernel<true, true, true> : temporal_kernel<false, true, true>)
+                                 : (tiles ? temporal_kernel<true, false, true> : temporal_kernel<false, false, true>))
+                    : (t.mom_out ? (tiles ? temporal_kernel<true, true, false> : temporal_kernel<false, true, false>)
+                                 : (tiles ? temporal_kernel<true, false, false> : temporal_kernel<false, false, false>));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(tx * ty)), dim3(256), 0, stream, t, (int)tx,
+                       motion ? *motion : TemporalMotion{});
     return hipGetLastError();
 }
 

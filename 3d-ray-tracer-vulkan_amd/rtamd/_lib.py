@@ -43,7 +43,7 @@ EXPORTED = (
     "rt_temporal_default_params", "rt_temporal_camera_basis", "rt_temporal_device", "rt_render_temporal",
     "rt_denoise_history_device", "rt_render_temporal_adaptive",
     "rt_temporal_moments_device", "rt_variance_default_params", "rt_denoise_variance_device",
-    "rt_render_temporal_variance",
+    "rt_render_temporal_variance", "rt_temporal_motion_device",
     "rt_learn_device", "rt_learn_copy",
     "rt_samples_workspace_bytes", "rt_render_samples_device", "rt_render_samples",
     "rt_update_geometry", "rt_refit_scene", "rt_accel_refit_records", "rt_scene_copy_records",
@@ -54,7 +54,7 @@ EXPORTED = (
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
                  "csrc/rt_filter.hip", "csrc/rt_temporal.hip", "csrc/rt_samples.hip", "csrc/rt_refit.hip",
                  "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h", "csrc/rt_pixel.h",
-                 "csrc/accel_build.h", "../include/rtamd.h")
+                 "csrc/accel_build.h", "csrc/temporal_motion_host.h", "../include/rtamd.h")
 
 
 def source_hash() -> str:
@@ -261,6 +261,9 @@ def lib() -> C.CDLL:
                                                       C.POINTER(DenoiseParams), C.c_uint32, vp, vp, C.POINTER(Stats)]),
                 "rt_temporal_moments_device": (i32, [vp, i32, i32, C.POINTER(CameraUBO), vp, vp, C.POINTER(CameraUBO), vp,
                                                      vp, C.POINTER(TemporalParams), vp, vp, vp, vp, dp, vp, vp]),
+                "rt_temporal_motion_device": (i32, [vp, i32, i32, C.POINTER(CameraUBO), vp, vp, C.POINTER(CameraUBO), vp,
+                                                    vp, C.POINTER(TemporalParams), vp, vp, vp, vp, dp, vp, vp, vp, vp,
+                                                    sz]),
                 "rt_variance_default_params": (None, [C.POINTER(VarianceParams)]),
                 "rt_denoise_variance_device": (i32, [vp, i32, i32, vp, vp, vp, C.POINTER(VarianceParams), vp, vp, vp, vp,
                                                      dp]),

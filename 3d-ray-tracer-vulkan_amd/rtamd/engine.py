@@ -348,6 +348,28 @@ class Renderer:
             C.byref(t) if t is not None else None, d_mom_prev, d_mom_out))
         return t.value if t is not None else None
 
+    def temporal_motion_device(self, width: int, height: int, camera, d_radiance: int, d_hits: int, d_hist_out: int,
+                               prev_camera=None, d_hist_prev: Optional[int] = None, d_hits_prev: Optional[int] = None,
+                               d_verts_cur: Optional[int] = None, d_verts_prev: Optional[int] = None, n_tris: int = 0,
+                               d_mom_prev: Optional[int] = None, d_mom_out: Optional[int] = None,
+                               d_out_rgba: Optional[int] = None, d_out_radiance: Optional[int] = None,
+                               params: Optional[TemporalParams] = None, stream: Optional[int] = None,
+                               ms: bool = False):
+        """temporal_device across a geometry update (rt_temporal_motion_device,
+        DESIGN.md §4m): d_verts_cur and d_verts_prev are the vertex records (48
+        bytes per flattened triangle) as the new and the previous frame's hit
+        records saw them, n_tris the triangles both hold; the history is
+        gathered where each pixel's point of its triangle lay before the
+        update.  Both None: temporal_device, or with the moments buffers
+        temporal_moments_device, bit for bit."""
+        t = C.c_double() if ms else None
+        check(lib().rt_temporal_motion_device(
+            self._ctx, width, height, C.byref(_ubo(camera)) if camera is not None else None, d_radiance, d_hits,
+            C.byref(_ubo(prev_camera)) if prev_camera is not None else None, d_hist_prev, d_hits_prev,
+            C.byref(params) if params is not None else None, d_hist_out, d_out_rgba, d_out_radiance, stream,
+            C.byref(t) if t is not None else None, d_mom_prev, d_mom_out, d_verts_cur, d_verts_prev, n_tris))
+        return t.value if t is not None else None
+
     def denoise_variance_device(self, width: int, height: int, d_hist: int, d_mom: int, d_hits: int, d_workspace: int,
                                 d_out_rgba: Optional[int] = None, d_out_radiance: Optional[int] = None,
                                 params: Optional[VarianceParams] = None, stream: Optional[int] = None,
@@ -551,7 +573,8 @@ class HipEngine:
                  height: int = REFERENCE_HEIGHT, max_bounces: int = REFERENCE_MAX_BOUNCES,
                  device_ids: Sequence[int] = (0,), collect_stats: bool = False, pipelined: bool = True,
                  inflight: int = 4, denoise: Optional[DenoiseParams] = None,
-                 temporal: Optional[TemporalParams] = None, adaptive: bool = False, variance=None):
+                 temporal: Optional[TemporalParams] = None, adaptive: bool = False, variance=None,
+                 motion: bool = False):
         self.frame_queue = frame_queue
         # pipelined: `inflight` frames in flight (rt_render_async, one slot and
         # trace stream each), so the frames' traces overlap each other and
@@ -565,17 +588,21 @@ class HipEngine:
         # temporal None = the default parameters, denoise = the filter's parameters or None for its defaults).
         # variance (True or a VarianceParams): the temporal path with the variance-guided filter
         # (render_temporal's variance=; temporal None = the default parameters).
+        # motion: scenes are uploaded with options refit and temporal_motion 1, so that a geometry update
+        # (submit_geometry_update) keeps the temporal history and the next frame reprojects it per triangle.
+        self.motion = bool(motion)
         self.denoise = denoise
         self.variance = None if variance is False else variance
         self.temporal = TemporalParams() if (adaptive or self.variance is not None) and temporal is None else temporal
         self.adaptive = bool(adaptive)
         self.temporal_frames = 0
+        self.geometry_updates = 0
         self.pipelined = pipelined and not collect_stats and denoise is None and self.temporal is None
         self.inflight = max(1, min(8, int(inflight)))
         self.width, self.height, self.max_bounces = width, height, max_bounces
         self.device_ids = tuple(device_ids)
         self.collect_stats = collect_stats
-        self._scene_q: "queue.Queue[BuiltCpuData]" = queue.Queue()
+        self._scene_q: "queue.Queue[tuple]" = queue.Queue()     # (BuiltCpuData, True for a geometry update)
         self._camera_q: "queue.Queue[Camera]" = queue.Queue()
         self._sky_q: "queue.Queue[bool]" = queue.Queue()
         self._running = False
@@ -595,7 +622,15 @@ class HipEngine:
         self._thread.join(5.0)          # 5 s graceful window, VulkanEngine.java:145
 
     def submit_scene(self, scene_data: BuiltCpuData) -> None:
-        self._scene_q.put(scene_data)
+        self._scene_q.put((scene_data, False))
+
+    def submit_geometry_update(self, built: BuiltCpuData) -> None:
+        """The current scene's triangles moved (rtamd.refit_buffers of the
+        submitted scene): queued like a scene and applied on the render thread
+        through Renderer.update_geometry, after the frames in flight.  The
+        engine must have been made with motion=True, which uploads scenes with
+        the refit tables."""
+        self._scene_q.put((built, True))
 
     def submit_camera_update(self, camera: Camera) -> None:
         self._camera_q.put(camera)
@@ -610,14 +645,21 @@ class HipEngine:
         try:
             renderer = Renderer(self.device_ids)
             renderer.set_option("async_slots", self.inflight)
+            if self.motion:
+                renderer.set_option("refit", 1)
+                renderer.set_option("temporal_motion", 1)
             have_scene, camera = False, None
             while self._running:
                 try:                                        # one scene per pass (:281-285)
-                    scene = self._scene_q.get_nowait()
+                    scene, update = self._scene_q.get_nowait()
                     while pending:                          # frames of the old scene first
                         self._finish(renderer, slots, pending.pop(0))
-                    renderer.upload_scene(scene)
-                    have_scene = True
+                    if update:
+                        renderer.update_geometry(scene)
+                        self.geometry_updates += 1
+                    else:
+                        renderer.upload_scene(scene)
+                        have_scene = True
                 except queue.Empty:
                     pass
                 while True:                                 # drain to the latest camera (:288-298)

@@ -281,8 +281,10 @@ int rt_render_poll(rt_ctx* ctx, uint64_t ticket, int* done);
  * tri_tests are those of the walk over the refitted records (on the accel
  * tree: rt_accel_refit_records' of the uploaded scene's records).  The call
  * waits for every device of the context, refits each of them, drops the
- * temporal history and the samples sum as rt_upload_scene does, and keeps the
- * learned tile orders and heavy pixels (results never depend on them).
+ * temporal history and the samples sum as rt_upload_scene does (with option
+ * "temporal_motion" 1 the history stays and the next temporal frame
+ * reprojects it per triangle, see the options), and keeps the learned tile
+ * orders and heavy pixels (results never depend on them).
  * ms (nullable): the device time of the refit kernels on device 0 (HIP events).
  * Errors, the scene unchanged in every case: RT_ERR_NO_SCENE;
  * RT_ERR_INVALID_ARG for a null pointer or a scene without refit tables
@@ -650,6 +652,41 @@ int rt_render_temporal_variance(rt_ctx* ctx, const rt_camera_ubo* cam, int width
                                 const rt_temporal_params* tparams, const rt_variance_params* vparams, uint32_t flags,
                                 uint8_t* out_rgba, float* out_radiance, rt_stats* stats);
 
+/* ------------------------------------- temporal history across an update -- */
+/* NON-REFERENCE: the accumulation when triangles moved between the two frames
+ * (rt_update_geometry keeps the flattened triangle order, so a hit record's
+ * tri names the same triangle in both).  rt_temporal_moments_device's
+ * arguments plus the vertex records (RT_VERTEX_RECORD_BYTES per flattened
+ * triangle, three float4 whose w is ignored, 16-byte aligned DEVICE buffers,
+ * never written) as the new frame's hit records saw them (d_verts_cur) and as
+ * the previous frame's did (d_verts_prev), and the triangles both hold.  A
+ * pixel's hit point is expressed in the barycentric coordinates of its
+ * triangle in d_verts_cur and evaluated on that triangle in d_verts_prev: the
+ * point P' and the normal n' found there take the place of the pixel's
+ * position and normal on the previous-frame side of rt_temporal_device's
+ * contract (the projection through prev_cam and the taps' two tests).  A
+ * triangle whose nine coordinates are bit for bit the same in both buffers is
+ * rt_temporal_device exactly.  A pixel whose tri is n_tris or more, or whose
+ * P' or n' is not finite (a degenerate triangle), starts again from its own
+ * sample.  The contract operation by operation is DESIGN.md §4m
+ * (tests/temporal_motion_ref.py restates it in numpy, bit for bit).
+ * d_mom_prev and d_mom_out both NULL: no moments (rt_temporal_device's
+ * outputs); else as rt_temporal_moments_device.  d_verts_cur and d_verts_prev
+ * both NULL: the call is rt_temporal_device or rt_temporal_moments_device, the
+ * same kernels and bits, and n_tris is ignored.  Additional
+ * RT_ERR_INVALID_ARG: one vertex buffer without the other, vertex buffers
+ * without a previous frame, one not 16-byte aligned, n_tris 0 or above 2^29,
+ * an output overlapping a vertex buffer.  Option "temporal_tile" applies.
+ * Added at ABI version 6 without a bump: no existing struct or argument list
+ * changed. */
+int rt_temporal_motion_device(rt_ctx* ctx, int width, int height,
+                              const rt_camera_ubo* cam, const float* d_radiance, const rt_hit* d_hits,
+                              const rt_camera_ubo* prev_cam, const void* d_hist_prev, const rt_hit* d_hits_prev,
+                              const rt_temporal_params* params,
+                              void* d_hist_out, void* d_out_rgba, float* d_out_radiance, void* stream, double* ms,
+                              const void* d_mom_prev, void* d_mom_out,
+                              const void* d_verts_cur, const void* d_verts_prev, size_t n_tris);
+
 /* ---------------------------------------------------------------- samples -- */
 /* NON-REFERENCE: several samples per pixel in one call.  Extension bit 4
  * averages one sample per launch; here one trace launch carries up to 16
@@ -945,6 +982,33 @@ int rt_render_samples(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int heig
  *                   Same results; 1 and 2 are for tests and
  *                   tools/temporal_bench.py.  Applies to
  *                   rt_temporal_moments_device in the same way
+ *   "temporal_motion" NON-REFERENCE, 0 (default) / 1: rt_update_geometry keeps
+ *                   the history of the rt_render_temporal* calls instead of
+ *                   dropping it (one-device contexts; the samples sum is
+ *                   still dropped).  At the first update since the last
+ *                   temporal frame it copies the vertex records that frame saw
+ *                   into a device buffer of 48 B per flattened triangle
+ *                   (allocated then), so several updates between two frames
+ *                   reproject from the right state; the next
+ *                   rt_render_temporal, _adaptive or _variance call runs
+ *                   rt_temporal_motion_device with that copy and the current
+ *                   records.  A frame with no update since the last one
+ *                   launches what it always did.  RT_TEMPORAL_RESET,
+ *                   rt_upload_scene, rt_upload_spheres, another frame size
+ *                   and a change of history kind drop the history and the
+ *                   copy as before; a refused update changes nothing.  The
+ *                   records before a scene's first update are copied to the
+ *                   refit staging buffer by an rt_upload_scene made with the
+ *                   option on (one more copy of the caller's vertex buffer;
+ *                   with 0 an upload is what it always was): when the option
+ *                   is turned on after the upload, the scene's first update
+ *                   still drops the history.  Read by rt_upload_scene,
+ *                   rt_update_geometry and the rt_render_temporal* calls; a
+ *                   frame that finds a kept history with the option off drops
+ *                   it
+ *   "temporal_motion_used" (rt_get_option only) 1 when the last
+ *                   rt_render_temporal* call ran rt_temporal_motion_device's
+ *                   kernel
  *   "variance_stage" rt_denoise_variance_device: 0 = only the variance
  *                   estimate is enqueued (tools/variance_bench.py times it
  *                   this way; the outputs are not written); -1 (default) =

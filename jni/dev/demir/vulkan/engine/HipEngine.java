@@ -26,6 +26,7 @@ public class HipEngine implements Runnable {
     private final ConcurrentLinkedQueue<Object[]> pickQueue = new ConcurrentLinkedQueue<>();
     private final ConcurrentLinkedQueue<ByteBuffer[]> geometryQueue = new ConcurrentLinkedQueue<>();
     private volatile boolean refit = false;                               // setRefit: uploads keep the refit tables
+    private volatile boolean temporalMotion = false;                      // setTemporalMotion: updates keep the history
     private long ctx = 0;
     private boolean haveScene = false;
     private ByteBuffer[] slots = null;
@@ -57,6 +58,10 @@ public class HipEngine implements Runnable {
     public void submitSkyToggle(boolean on) { skyToggleQueue.add(on); }
     /** Scenes submitted from now on keep what submitGeometryUpdate needs (rt option "refit"). */
     public void setRefit(boolean on) { refit = on; }
+    /** With setTemporal and setRefit: a geometry update keeps the temporal history, and the next frame gathers it
+     *  where each pixel's point of its triangle lay before the update (rt option "temporal_motion").  Takes
+     *  effect with the next submitted scene, like setRefit. */
+    public void setTemporalMotion(boolean on) { temporalMotion = on; }
     /** The current scene's triangles moved (an object dragged): the moved vertex records in the uploaded order and
      *  the uploaded nodes with new boxes, as direct buffers whose capacities are their byte sizes (rt_refit_scene
      *  writes both).  Applied on the render thread before its next frame (rt_update_geometry); only the newest
@@ -102,6 +107,7 @@ public class HipEngine implements Runnable {
                 if (d != null) {
                     geometryQueue.clear();                                // updates of the scene this one replaces
                     HipNative.setOption(ctx, "refit", refit ? 1 : 0);
+                    HipNative.setOption(ctx, "temporal_motion", temporalMotion ? 1 : 0);
                     HipNative.uploadScene(ctx, memByteBufferOf(d.modelVertexData), d.modelVertexData.remaining() * 4L,
                                           memByteBufferOf(d.modelMaterialData), d.modelMaterialData.remaining() * 4L,
                                           d.flatBvhData, d.flatBvhData.remaining());
