@@ -405,4 +405,28 @@ struct RefitArgs {
 // Enqueues the three stages on `stream`; level_first: n_levels + 1 offsets into by_height (host memory).
 hipError_t launch_refit(const RefitArgs& r, const int* level_first, int n_levels, hipStream_t stream);
 
+// rt_update_geometry_device (option refit_device): rt_refit_scene restated on the device.
+// The input triangles are read from device memory, checked, and staged into st_verts / st_boxes as the
+// bytes rt_refit_scene writes; launch_refit then runs on the staged arrays as after a host update.
+struct RefitFront {
+    const void*     in = nullptr;        // n_in * 9 doubles (f32: floats): v0, v1, v2 of each input triangle
+    const uint32_t* source = nullptr;    // flattened triangle f copies input triangle source[f]; null: f itself
+    size_t          n_in = 0;
+    int             f32 = 0;
+    int             n_flat = 0;          // flattened triangles of the scene
+    float4*         st_verts = nullptr;  // RefitTables' staging arrays
+    float*          st_boxes = nullptr;
+    const int*      ref_info = nullptr;  // RefitTables::ref_info
+    const int*      by_height = nullptr; // the reference nodes of the root's subtree by height, leaves first
+    const int*      dups = nullptr;      // 4 per dropped duplicate: its triangle and reference leaf, its keeper's
+    int             n_dups = 0;
+    unsigned*       status = nullptr;    // kRefitStatusWords words: the lowest offending flattened triangle per kind
+};
+constexpr int kRefitStatusWords = 4;     // [0] a source entry >= n_in, [1] a cast that is not finite,
+                                         // [2] a dropped duplicate that no longer is one, [3] unused
+// The check: reads the input only, and sets status (every word 0xFFFFFFFF where nothing offends).
+hipError_t launch_refit_check(const RefitFront& f, hipStream_t stream);
+// The stage kernel, the leaf boxes and one launch per level; level_first: n_levels + 1 offsets into by_height.
+hipError_t launch_refit_front(const RefitFront& f, const int* level_first, int n_levels, hipStream_t stream);
+
 }  // namespace rtamd

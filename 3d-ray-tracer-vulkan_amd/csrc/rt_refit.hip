@@ -25,6 +25,12 @@
 // No lane waits for another: a level's inputs were written by earlier
 // launches of the same stream.  min and max are order-free, so the result
 // does not depend on scheduling.  Bandwidth bound; no LDS, no atomics.
+//
+// rt_update_geometry_device fills the two staging arrays on
+// the device instead, from input triangles in device memory: the refit_in_*
+// kernels further down (a check that only reads, with an atomicMin per
+// offender; the records; the leaf boxes in double; one launch per level of the
+// reference's tree), in front of the same three stages.
 #include "rt_internal.h"
 
 #include "accel_build.h"
@@ -158,7 +164,171 @@ __global__ __launch_bounds__(256) void refit_level(RefitArgs r, int first, int c
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// rt_update_geometry_device: rt_refit_scene (scene_build.cpp) restated here, operation
+// for operation in double, so that st_verts and st_boxes hold the bytes the host path stages.
+//   refit_in_check  : reads the input only.  A lane per flattened triangle: its source entry and the
+//                     nine float casts; the first lanes also take a (dropped, kept) pair each.  The
+//                     lowest offender of each kind goes into a status word (a vector-memory atomicMin).
+//   refit_in_stage  : a lane per flattened triangle: its 48-B record.
+//   refit_in_leaves : a lane per reference leaf: Triangle.calculateBoundingBox in double, cast once.
+//   refit_in_level  : one launch per height: a lane per node, the union of its children's boxes.
+// The union is taken of the children's float boxes: rounding to float is monotone, so the cast of the
+// smaller double is the smaller (or an equal) float, and Math.min / Math.max pick -0.0 / +0.0 among
+// zeros by sign alone, which the cast keeps (a double too small for a float becomes a zero of its sign).
+// So min(cast a, cast b) has the bytes of cast(min(a, b)), and no double boxes are kept.
+
+// java.lang.Math.min / max (scene_build.cpp jmin / jmax): NaN wins, -0.0 < +0.0
+__device__ __forceinline__ double jmin(double a, double b) {
+    if (a != a) return a;
+    if (a == 0.0 && b == 0.0) return __double_as_longlong(a) < 0 ? a : b;
+    return a <= b ? a : b;
+}
+__device__ __forceinline__ double jmax(double a, double b) {
+    if (a != a) return a;
+    if (a == 0.0 && b == 0.0) return __double_as_longlong(a) < 0 ? b : a;
+    return a >= b ? a : b;
+}
+__device__ __forceinline__ float jminf(float a, float b) {
+    if (a != a) return a;
+    if (a == 0.f && b == 0.f) return (int)bits(a) < 0 ? a : b;
+    return a <= b ? a : b;
+}
+__device__ __forceinline__ float jmaxf(float a, float b) {
+    if (a != a) return a;
+    if (a == 0.f && b == 0.f) return (int)bits(a) < 0 ? b : a;
+    return a >= b ? a : b;
+}
+
+template <bool F32>
+__device__ __forceinline__ void load_in(const RefitFront& f, size_t tri, double v[9]) {
+    for (int k = 0; k < 9; ++k)
+        v[k] = F32 ? (double)static_cast<const float*>(f.in)[9 * tri + k] : static_cast<const double*>(f.in)[9 * tri + k];
+}
+
+struct BoxF { float lo[3], hi[3]; };
+
+// tri_box (scene_build.cpp) of 9 doubles, cast as write_node casts it
+__device__ __forceinline__ BoxF tri_box(const double v[9]) {
+    const double eps = 0.0001;                 // Triangle.java:65
+    double mn[3], mx[3];
+    for (int k = 0; k < 3; ++k) {
+        mn[k] = jmin(v[k], jmin(v[3 + k], v[6 + k]));
+        mx[k] = jmax(v[k], jmax(v[3 + k], v[6 + k]));
+    }
+    // each add touches all three components (x + 0.0 turns -0.0 into +0.0)
+    for (int k = 0; k < 3; ++k)
+        if (mx[k] - mn[k] < eps)
+            for (int j = 0; j < 3; ++j) mx[j] = mx[j] + (j == k ? eps : 0.0);
+    BoxF b;
+    for (int k = 0; k < 3; ++k) {
+        b.lo[k] = (float)mn[k];
+        b.hi[k] = (float)mx[k];
+    }
+    return b;
+}
+
+__device__ __forceinline__ bool finite_bits(float x) { return (bits(x) & 0x7F800000u) != 0x7F800000u; }
+
+template <bool F32>
+__global__ __launch_bounds__(256) void refit_in_check(RefitFront f) {
+    const unsigned g = blockIdx.x * 256u + threadIdx.x;
+    if (g < (unsigned)f.n_flat) {
+        const size_t src = f.source ? f.source[g] : g;
+        if (src >= f.n_in) {
+            atomicMin(f.status + 0, g);
+        } else {
+            double v[9];
+            load_in<F32>(f, src, v);
+            bool ok = true;
+            for (int k = 0; k < 9; ++k) ok = ok && finite_bits((float)v[k]);
+            if (!ok) atomicMin(f.status + 1, g);
+        }
+    }
+    if (g < (unsigned)f.n_dups) {
+        const unsigned dropped = (unsigned)f.dups[4 * (size_t)g], kept = (unsigned)f.dups[4 * (size_t)g + 2];
+        const size_t sa = f.source ? f.source[dropped] : dropped, sb = f.source ? f.source[kept] : kept;
+        if (sa >= f.n_in || sb >= f.n_in) return;          // status[0] has it: both are flattened triangles
+        double a[9], b[9];
+        load_in<F32>(f, sa, a);
+        load_in<F32>(f, sb, b);
+        bool same = true;
+        for (int k = 0; k < 9; ++k) same = same && bits((float)a[k]) == bits((float)b[k]);
+        const BoxF ba = tri_box(a), bb = tri_box(b);
+        for (int k = 0; k < 3; ++k) same = same && bits(ba.lo[k]) == bits(bb.lo[k]) && bits(ba.hi[k]) == bits(bb.hi[k]);
+        if (!same) atomicMin(f.status + 2, dropped);
+    }
+}
+
+template <bool F32>
+__global__ __launch_bounds__(256) void refit_in_stage(RefitFront f) {
+    const unsigned g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= (unsigned)f.n_flat) return;
+    double v[9];
+    load_in<F32>(f, f.source ? f.source[g] : g, v);
+    float4* o = f.st_verts + 3 * (size_t)g;
+    o[0] = make_float4((float)v[0], (float)v[1], (float)v[2], 0.0f);
+    o[1] = make_float4((float)v[3], (float)v[4], (float)v[5], 0.0f);
+    o[2] = make_float4((float)v[6], (float)v[7], (float)v[8], 0.0f);
+}
+
+template <bool F32>
+__global__ __launch_bounds__(256) void refit_in_leaves(RefitFront f, int count) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= count) return;
+    const int node = f.by_height[i];
+    const unsigned tri = (unsigned)f.ref_info[node];       // a leaf: its flattened triangle
+    double v[9];
+    load_in<F32>(f, f.source ? f.source[tri] : tri, v);
+    const BoxF b = tri_box(v);
+    float* o = f.st_boxes + 6 * (size_t)node;
+    for (int k = 0; k < 3; ++k) {
+        o[k] = b.lo[k];
+        o[3 + k] = b.hi[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void refit_in_level(RefitFront f, int first, int count) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= count) return;
+    const int node = f.by_height[first + i];
+    const float* L = f.st_boxes + 6 * ((size_t)node + 1);                      // AABB.surroundingBox(left, right)
+    const float* R = f.st_boxes + 6 * (size_t)(-(f.ref_info[node] + 1));
+    float* o = f.st_boxes + 6 * (size_t)node;
+    for (int k = 0; k < 3; ++k) {
+        o[k] = jminf(L[k], R[k]);
+        o[3 + k] = jmaxf(L[3 + k], R[3 + k]);
+    }
+}
+
 }  // namespace
+
+hipError_t launch_refit_check(const RefitFront& f, hipStream_t stream) {
+    const int n = f.n_flat > f.n_dups ? f.n_flat : f.n_dups;
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (f.f32) hipLaunchKernelGGL(refit_in_check<true>, grid, block, 0, stream, f);
+    else hipLaunchKernelGGL(refit_in_check<false>, grid, block, 0, stream, f);
+    return hipGetLastError();
+}
+
+hipError_t launch_refit_front(const RefitFront& f, const int* level_first, int n_levels, hipStream_t stream) {
+    const dim3 block(256);
+    if (f.n_flat > 0) {
+        const dim3 grid((unsigned)((f.n_flat + 255) / 256));
+        if (f.f32) hipLaunchKernelGGL(refit_in_stage<true>, grid, block, 0, stream, f);
+        else hipLaunchKernelGGL(refit_in_stage<false>, grid, block, 0, stream, f);
+    }
+    for (int h = 0; h < n_levels; ++h) {
+        const int first = level_first[h], count = level_first[h + 1] - first;
+        if (count <= 0) continue;
+        const dim3 grid((unsigned)((count + 255) / 256));
+        if (h > 0) hipLaunchKernelGGL(refit_in_level, grid, block, 0, stream, f, first, count);
+        else if (f.f32) hipLaunchKernelGGL(refit_in_leaves<true>, grid, block, 0, stream, f, count);
+        else hipLaunchKernelGGL(refit_in_leaves<false>, grid, block, 0, stream, f, count);
+    }
+    return hipGetLastError();
+}
 
 hipError_t launch_refit(const RefitArgs& r, const int* level_first, int n_levels, hipStream_t stream) {
     const RefitTables& t = r.t;

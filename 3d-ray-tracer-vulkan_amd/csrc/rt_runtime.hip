@@ -4,6 +4,7 @@
 // barriers, staging image) has no counterpart: device buffers + one HIP
 // stream per device.
 #include "rt_internal.h"
+#include "refit_levels_host.h"
 #include "temporal_motion_host.h"
 
 #include "accel_build.h"
@@ -350,6 +351,9 @@ struct PerDevice {
     char*        d_refit = nullptr;
     size_t       refit_bytes = 0;
     RefitTables  refit;
+    // option refit_device: rt_update_geometry_device's tables inside d_refit (by_height,
+    // dups, status; the input and the staging pointers are filled in per call), null without them
+    RefitFront   front;
     // option temporal_motion: the bookkeeping (temporal_motion_host.h) of refit.st_verts,
     // which holds the scene's current vertex records once staged, and of d_verts_prev (48 B per flattened
     // triangle, allocated at the first update of a scene that keeps the history), which holds them as the
@@ -509,6 +513,8 @@ struct rt_ctx {
                                    //   per wave, walked cooperatively, in a separate launch
                                    //   (-1 = automatic: the tiles that outlast the bulk, learn_order)
     int  refit = 0;                // at the next upload: keep what rt_update_geometry needs
+    int  refit_device = 0;         // at the next upload, with refit: the tables of rt_update_geometry_device too
+                                   //   
     int  temporal_motion = 0;      // rt_update_geometry keeps rt_render_temporal's history and the next temporal
                                    //   frame reprojects it per triangle
     // The host side of those tables: the uploaded buffers' sizes, every node's 24 bytes outside its boxes
@@ -519,6 +525,10 @@ struct rt_ctx {
     std::vector<uint8_t> refit_links;
     std::vector<int32_t> refit_dups;
     std::vector<int> refit_level_first;
+    // option refit_device: the current scene holds rt_update_geometry_device's tables, and where each
+    // height's nodes start in RefitFront::by_height (refit_levels_host.h)
+    bool refit_device_held = false;
+    std::vector<int> refit_front_first;
     uint64_t scene_gen = 0;        // bumped by every scene upload (invalidates learned tile orders)
     int  hw_queues = 4;            // GPU_MAX_HW_QUEUES seen at rt_create (HIP's default 4); frames in
                                    //   flight on more streams than queues - 2 share queues and serialise
@@ -540,6 +550,7 @@ static void free_scene(PerDevice& p) {
     p.d_refit = nullptr;
     p.refit_bytes = 0;
     p.refit = RefitTables{};
+    p.front = RefitFront{};
     if (p.d_verts_prev) (void)hipFree(p.d_verts_prev);
     p.d_verts_prev = nullptr;
     p.motion = MotionBook{};
@@ -1184,6 +1195,64 @@ static CamF cam_from_ubo(const rt_camera_ubo* c) {
     return f;
 }
 
+// One device's part of a geometry update, written once for rt_update_geometry and
+// rt_update_geometry_device (`who` in messages): the wait for the device, the caller's `check` (which may
+// still refuse: nothing is changed before it passes), the temporal history and the samples sum, the
+// caller's `stage` (st_verts and st_boxes filled on the stream given), the three refit stages, and the
+// root box (root_box, or null to read it from st_boxes).  The learned orders and scene_gen stay.
+// ms (nullable): the device time of the refit stages, and of `stage` too with time_stage.
+static int no_check() { return RT_OK; }
+
+template <class Check, class Stage>
+static int update_on_device(rt_ctx* ctx, PerDevice& p, const char* who, Check&& check, Stage&& stage, bool time_stage,
+                            const float* root_box, double* ms) {
+    const size_t n_nodes = (size_t)ctx->n_nodes, n_tris = (size_t)ctx->n_tris;
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    RT_HIP_CHECK(hipDeviceSynchronize());            // frames in flight read the records rewritten below
+    const int rc = check();
+    if (rc != RT_OK) return rc;
+    // Option temporal_motion: the history stays, and the records the last temporal frame
+    // saw are kept beside it, copied at the first update since that frame only.
+    bool copy = false;
+    const bool keep = p.motion.on_update(ctx->temporal_motion != 0, ctx->dev.size(), p.temporal_valid, n_tris, n_nodes,
+                                         &copy);
+    if (copy) {
+        if (!p.d_verts_prev) {
+            const hipError_t e = hipMalloc(&p.d_verts_prev, 48 * n_tris);
+            if (e != hipSuccess) {
+                p.d_verts_prev = nullptr;
+                p.motion.on_history_dropped();
+                p.temporal_valid = false;
+                set_error("%s: %zu bytes for the previous vertex records: %s", who, 48 * n_tris, hipGetErrorString(e));
+                return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+            }
+        }
+        RT_HIP_CHECK(hipMemcpyAsync(p.d_verts_prev, p.refit.st_verts, 48 * n_tris, hipMemcpyDeviceToDevice, p.stream));
+    }
+    if (!keep) p.temporal_valid = false;             // rt_render_temporal starts a new sequence
+    p.samples_held = 0;                              // and rt_render_samples a new sum
+    if (n_nodes == 0) return RT_OK;                  // an empty scene stays empty
+    const bool timed = ms != nullptr;
+    if (timed && time_stage) RT_HIP_CHECK(hipEventRecord(p.ev0, p.stream));
+    RT_HIP_CHECK(stage(p.stream));
+    RefitArgs r;
+    r.scene = p.scene;
+    r.t = p.refit;
+    if (timed && !time_stage) RT_HIP_CHECK(hipEventRecord(p.ev0, p.stream));
+    RT_HIP_CHECK(launch_refit(r, ctx->refit_level_first.data(), (int)ctx->refit_level_first.size() - 1, p.stream));
+    if (timed) RT_HIP_CHECK(hipEventRecord(p.ev1, p.stream));
+    RT_HIP_CHECK(hipStreamSynchronize(p.stream));
+    if (timed) {
+        float t = 0.f;
+        RT_HIP_CHECK(hipEventElapsedTime(&t, p.ev0, p.ev1));
+        *ms = t;
+    }
+    if (root_box) std::memcpy(p.scene.root_box, root_box, sizeof p.scene.root_box);
+    else RT_HIP_CHECK(hipMemcpy(p.scene.root_box, p.refit.st_boxes, sizeof p.scene.root_box, hipMemcpyDeviceToHost));
+    p.motion.after_update(n_tris);                   // the staging array now holds the scene's records
+    return RT_OK;
+}
+
 extern "C" {
 
 const char* rt_last_error(void) { return g_err; }
@@ -1461,6 +1530,9 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
     // Option refit: what rt_update_geometry needs, laid out once as the bytes every device
     // gets behind its staging buffers.  The half and wide record formats hold none.
     ctx->refit_held = false;
+    ctx->refit_device_held = false;
+    bool front = false;
+    size_t o_fheight = 0, o_fdups = 0, o_fstatus = 0;
     const bool keep = ctx->refit && !(acc && ah.format != 0);
     std::vector<uint8_t> rtab;                 // the tables, sections 16-B aligned
     size_t o_info = 0, o_slot = 0, o_prim = 0, o_child = 0, o_lslot = 0, o_height = 0, o_canon = 0;
@@ -1522,6 +1594,19 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
         ctx->refit_dups = acc ? ah.dup_pairs : std::vector<int32_t>();
         ctx->refit_vertex_bytes = vertex_bytes;
         ctx->refit_bvh_bytes = bvh_bytes;
+        // Option refit_device: the reference nodes by height, the dropped duplicates and
+        // the check's status words behind the tables above, which stay where they are without it
+        std::vector<int32_t> by_height;
+        front = ctx->refit_device != 0 &&
+                refit_levels(reinterpret_cast<const int32_t*>(rtab.data() + o_info), n2, &by_height, &ctx->refit_front_first);
+        if (front) {
+            o_fheight = section(4 * n2);
+            if (n2) std::memcpy(&rtab[o_fheight], by_height.data(), 4 * n2);
+            o_fdups = section(4 * ctx->refit_dups.size());
+            if (!ctx->refit_dups.empty())
+                std::memcpy(&rtab[o_fdups], ctx->refit_dups.data(), 4 * ctx->refit_dups.size());
+            o_fstatus = section(sizeof(unsigned) * kRefitStatusWords);
+        }
     }
     ctx->has_scene = false;
     for (PerDevice& p : ctx->dev) {
@@ -1628,6 +1713,17 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
                 t.by_height = reinterpret_cast<const int*>(tb + o_height);
                 t.canon = reinterpret_cast<float4*>(tb + o_canon);
             }
+            if (front) {
+                RefitFront& f = p.front;
+                f.n_flat = hs.n_tris;
+                f.st_verts = const_cast<float4*>(t.st_verts);
+                f.st_boxes = const_cast<float*>(t.st_boxes);
+                f.ref_info = t.ref_info;
+                f.by_height = reinterpret_cast<const int*>(tb + o_fheight);
+                f.dups = reinterpret_cast<const int*>(tb + o_fdups);
+                f.n_dups = (int)(ctx->refit_dups.size() / 4);
+                f.status = reinterpret_cast<unsigned*>(tb + o_fstatus);
+            }
         }
         // the padding memsets ran on the null stream: complete before any
         // launch stream (non-blocking) reads the scene
@@ -1646,6 +1742,7 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
     ctx->max_depth = hs.max_depth;
     ctx->has_scene = true;
     ctx->refit_held = keep;
+    ctx->refit_device_held = keep && front;
     ++ctx->scene_gen;
     for (PerDevice& p : ctx->dev) p.temporal_valid = false;   // rt_render_temporal starts a new sequence
     for (PerDevice& p : ctx->dev) p.samples_held = 0;         // and rt_render_samples a new sum
@@ -1714,53 +1811,133 @@ int rt_update_geometry(rt_ctx* ctx, const void* vertices, size_t vertex_bytes, c
     }
     if (ms) *ms = 0.0;
     for (PerDevice& p : ctx->dev) {
-        RT_HIP_CHECK(hipSetDevice(p.device));
-        RT_HIP_CHECK(hipDeviceSynchronize());            // frames in flight read the records rewritten below
-        // Option temporal_motion: the history stays, and the records the last temporal frame
-        // saw are kept beside it, copied at the first update since that frame only.
-        bool copy = false;
-        const bool keep = p.motion.on_update(ctx->temporal_motion != 0, ctx->dev.size(), p.temporal_valid, n_tris, n_nodes,
-                                             &copy);
-        if (copy) {
-            if (!p.d_verts_prev) {
-                const hipError_t e = hipMalloc(&p.d_verts_prev, 48 * n_tris);
-                if (e != hipSuccess) {
-                    p.d_verts_prev = nullptr;
-                    p.motion.on_history_dropped();
-                    p.temporal_valid = false;
-                    set_error("rt_update_geometry: %zu bytes for the previous vertex records: %s", 48 * n_tris,
-                              hipGetErrorString(e));
-                    return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
-                }
-            }
-            RT_HIP_CHECK(hipMemcpyAsync(p.d_verts_prev, p.refit.st_verts, 48 * n_tris, hipMemcpyDeviceToDevice,
-                                        p.stream));
-        }
-        if (!keep) p.temporal_valid = false;             // rt_render_temporal starts a new sequence
-        p.samples_held = 0;                              // and rt_render_samples a new sum
-        if (n_nodes == 0) continue;                      // an empty scene stays empty
-        if (n_tris)
-            RT_HIP_CHECK(hipMemcpyAsync(const_cast<float4*>(p.refit.st_verts), vb, 48 * n_tris, hipMemcpyHostToDevice,
-                                        p.stream));
-        RT_HIP_CHECK(hipMemcpyAsync(const_cast<float*>(p.refit.st_boxes), boxes.data(), 24 * n_nodes,
-                                    hipMemcpyHostToDevice, p.stream));
-        RefitArgs r;
-        r.scene = p.scene;
-        r.t = p.refit;
-        const bool timed = ms && &p == &ctx->dev[0];
-        if (timed) RT_HIP_CHECK(hipEventRecord(p.ev0, p.stream));
-        RT_HIP_CHECK(launch_refit(r, ctx->refit_level_first.data(), (int)ctx->refit_level_first.size() - 1, p.stream));
-        if (timed) RT_HIP_CHECK(hipEventRecord(p.ev1, p.stream));
-        RT_HIP_CHECK(hipStreamSynchronize(p.stream));
-        if (timed) {
-            float t = 0.f;
-            RT_HIP_CHECK(hipEventElapsedTime(&t, p.ev0, p.ev1));
-            *ms = t;
-        }
-        std::memcpy(p.scene.root_box, boxes.data(), sizeof p.scene.root_box);
-        p.motion.after_update(n_tris);                   // the staging array now holds the scene's records
+        const auto stage = [&](hipStream_t s) {
+            hipError_t e = hipSuccess;
+            if (n_tris)
+                e = hipMemcpyAsync(const_cast<float4*>(p.refit.st_verts), vb, 48 * n_tris, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(const_cast<float*>(p.refit.st_boxes), boxes.data(), 24 * n_nodes,
+                                   hipMemcpyHostToDevice, s);
+            return e;
+        };
+        const int rc = update_on_device(ctx, p, "rt_update_geometry", no_check, stage, false, boxes.data(),
+                                        ms && &p == &ctx->dev[0] ? ms : nullptr);
+        if (rc != RT_OK) return rc;
     }
     return RT_OK;
+}
+
+int rt_update_geometry_device(rt_ctx* ctx, const void* d_tri_verts, size_t n_tris, const uint32_t* d_source,
+                              size_t n_flat, uint32_t flags, double* ms) {
+    static const char who[] = "rt_update_geometry_device";
+    if (!ctx) { set_error("%s: null context", who); return RT_ERR_INVALID_ARG; }
+    if (!ctx->has_scene) { set_error("%s: no scene uploaded", who); return RT_ERR_NO_SCENE; }
+    if (flags & ~(uint32_t)RT_GEOM_F32) { set_error("%s: unknown flags 0x%x", who, flags); return RT_ERR_INVALID_ARG; }
+    if (ctx->dev.size() != 1) {
+        set_error("%s: a context of %zu devices (the input lives on one device)", who, ctx->dev.size());
+        return RT_ERR_INVALID_ARG;
+    }
+    if (!ctx->refit_device_held) {
+        const DevScene& sc = ctx->dev[0].scene;
+        if (sc.half || sc.wide)
+            set_error("%s: the scene's accel records are in the %s format, which is not refitted (upload without "
+                      "accel_%s)", who, sc.half ? "half" : "wide", sc.half ? "half" : "wide");
+        else
+            set_error("%s: the scene holds no device refit tables: set options refit and refit_device to 1 before "
+                      "rt_upload_scene", who);
+        return RT_ERR_INVALID_ARG;
+    }
+    const bool f32 = (flags & RT_GEOM_F32) != 0;
+    const size_t elem = f32 ? 4 : 8;
+    if (n_flat != (size_t)ctx->n_tris) {
+        set_error("%s: n_flat %zu, the uploaded scene has %d flattened triangles", who, n_flat, ctx->n_tris);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (!d_source && n_tris != n_flat) {
+        set_error("%s: without d_source the input is in flattened order: n_tris %zu is not n_flat %zu", who, n_tris, n_flat);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (n_tris == 0 && n_flat != 0) { set_error("%s: n_tris 0 for a scene of %zu triangles", who, n_flat); return RT_ERR_INVALID_ARG; }
+    if (n_tris > ((size_t)1 << 29)) { set_error("%s: n_tris %zu: at most 2^29", who, n_tris); return RT_ERR_INVALID_ARG; }
+    if (!d_tri_verts && n_tris != 0) { set_error("%s: null input", who); return RT_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_tri_verts % elem || (uintptr_t)d_source % 4) {
+        set_error("%s: d_tri_verts must be aligned to %zu bytes and d_source to 4", who, elem);
+        return RT_ERR_INVALID_ARG;
+    }
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    // both inputs must be device memory of this device, large enough for what the kernels read
+    const struct { const void* ptr; size_t bytes; const char* name; } inputs[2] = {
+        {d_tri_verts, n_tris * 9 * elem, "d_tri_verts"}, {d_source, n_flat * 4, "d_source"}};
+    for (const auto& in : inputs) {
+        if (!in.ptr || in.bytes == 0) continue;
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, in.ptr) != hipSuccess ||
+            (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != p.device) {
+            (void)hipGetLastError();
+            set_error("%s: %s is not device memory of device %d", who, in.name, p.device);
+            return RT_ERR_INVALID_ARG;
+        }
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)in.ptr) != hipSuccess) {
+            (void)hipGetLastError();            // an allocation the runtime cannot size: the caller's word stands
+            continue;
+        }
+        const size_t off = (size_t)((const char*)in.ptr - (const char*)base);
+        if (off > size || in.bytes > size - off) {
+            set_error("%s: %s: %zu bytes do not fit its allocation (%zu bytes from the pointer on)", who, in.name,
+                      in.bytes, size - off);
+            return RT_ERR_INVALID_ARG;
+        }
+    }
+    RefitFront f = p.front;
+    f.in = d_tri_verts;
+    f.source = d_source;
+    f.n_in = n_tris;
+    f.f32 = f32 ? 1 : 0;
+    const size_t n_nodes = (size_t)ctx->n_nodes;
+    double check_ms = 0.0;
+    // The checks, in rt_refit_scene's and rt_update_geometry's order; nothing is written before they pass.
+    const auto check = [&]() -> int {
+        if (n_nodes == 0 || n_flat == 0) return RT_OK;
+        unsigned st[kRefitStatusWords];
+        RT_HIP_CHECK(hipMemsetAsync(f.status, 0xFF, sizeof st, p.stream));
+        if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, p.stream));
+        RT_HIP_CHECK(launch_refit_check(f, p.stream));
+        if (ms) RT_HIP_CHECK(hipEventRecord(p.ev1, p.stream));
+        RT_HIP_CHECK(hipMemcpyAsync(st, f.status, sizeof st, hipMemcpyDeviceToHost, p.stream));
+        RT_HIP_CHECK(hipStreamSynchronize(p.stream));
+        if (ms) {
+            float t = 0.f;
+            RT_HIP_CHECK(hipEventElapsedTime(&t, p.ev0, p.ev1));
+            check_ms = t;
+        }
+        if (st[0] != 0xFFFFFFFFu) {
+            set_error("%s: flattened triangle %u copies an input triangle outside the %zu given", who, st[0], n_tris);
+            return RT_ERR_BAD_SCENE;
+        }
+        if (st[1] != 0xFFFFFFFFu) {
+            set_error("%s: triangle %u has a vertex that is not finite", who, st[1]);
+            return RT_ERR_BAD_SCENE;
+        }
+        if (st[2] != 0xFFFFFFFFu) {
+            int kept = -1;
+            for (size_t k = 0; k + 3 < ctx->refit_dups.size(); k += 4)
+                if ((unsigned)ctx->refit_dups[k] == st[2]) kept = ctx->refit_dups[k + 2];
+            set_error("%s: triangle %u was dropped at upload as a byte-identical copy of triangle %d "
+                      "and no longer is one: upload the scene again", who, st[2], kept);
+            return RT_ERR_BAD_SCENE;
+        }
+        return RT_OK;
+    };
+    const auto stage = [&](hipStream_t s) {
+        return launch_refit_front(f, ctx->refit_front_first.data(), (int)ctx->refit_front_first.size() - 1, s);
+    };
+    if (ms) *ms = 0.0;
+    const int rc = update_on_device(ctx, p, who, check, stage, true, nullptr, ms);
+    if (rc == RT_OK && ms) *ms += check_ms;
+    return rc;
 }
 
 int rt_scene_copy_records(rt_ctx* ctx, int which, uint32_t* out_words, size_t cap_words, size_t* n_words) {
@@ -3337,7 +3514,8 @@ static const Option kOptions[] = {
     one_of("accel", &rt_ctx::accel, 0, 1, 8),               //   rt_upload_scene
     one_of("accel_half", &rt_ctx::accel_half, 0, 1),
     one_of("accel_wide", &rt_ctx::accel_wide, 0, 1),
-    one_of("refit", &rt_ctx::refit, 0, 1),                  // and so does this one
+    one_of("refit", &rt_ctx::refit, 0, 1),                  // and so do these two
+    one_of("refit_device", &rt_ctx::refit_device, 0, 1),
     in_range("split_bounce", &rt_ctx::split_bounce, 0, 64),
     in_range("split_pixels", &rt_ctx::split_pixels, 0, 1 << 30),
     in_range("split_queues", &rt_ctx::split_queues, 1, kMaxSplitQueues),
@@ -3402,6 +3580,7 @@ int rt_get_option(rt_ctx* ctx, const char* name, int64_t* value) {
     else if (is("walk_bytes")) *value = p ? (int64_t)walk_bytes(*p) : 0;
     else if (is("refit_used")) *value = ctx->refit_held ? 1 : 0;
     else if (is("refit_bytes")) *value = p ? (int64_t)p->refit_bytes : 0;
+    else if (is("refit_device_used")) *value = ctx->refit_device_held ? 1 : 0;
     else if (is("temporal_motion_used")) *value = p ? p->motion_used : 0;
     else if (is("leaf_align_used")) *value = p ? p->scene.padded : 0;
     else if (is("heavy_pixels_used")) *value = p ? p->last_heavy_px : 0;

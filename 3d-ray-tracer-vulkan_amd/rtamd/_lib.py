@@ -47,6 +47,7 @@ EXPORTED = (
     "rt_learn_device", "rt_learn_copy",
     "rt_samples_workspace_bytes", "rt_render_samples_device", "rt_render_samples",
     "rt_update_geometry", "rt_refit_scene", "rt_accel_refit_records", "rt_scene_copy_records",
+    "rt_update_geometry_device",
 )
 
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
@@ -54,7 +55,7 @@ EXPORTED = (
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
                  "csrc/rt_filter.hip", "csrc/rt_temporal.hip", "csrc/rt_samples.hip", "csrc/rt_refit.hip",
                  "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h", "csrc/rt_pixel.h",
-                 "csrc/accel_build.h", "csrc/temporal_motion_host.h", "../include/rtamd.h")
+                 "csrc/accel_build.h", "csrc/temporal_motion_host.h", "csrc/refit_levels_host.h", "../include/rtamd.h")
 
 
 def source_hash() -> str:
@@ -163,6 +164,7 @@ class LearnInfo(C.Structure):           # rt_learn_info
 
 
 RT_QUERY_ANY = 1
+RT_GEOM_F32 = 1                 # rt_update_geometry_device's flags
 RT_TEMPORAL_RESET = 1           # rt_render_temporal's flags
 RT_TEMPORAL_FIXED_SEED = 2
 
@@ -276,6 +278,7 @@ def lib() -> C.CDLL:
                                                    C.POINTER(Stats)]),
                 "rt_render_samples": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, i32, vp, vp, C.POINTER(Stats)]),
                 "rt_update_geometry": (i32, [vp, vp, sz, vp, sz, dp]),
+                "rt_update_geometry_device": (i32, [vp, vp, sz, vp, sz, C.c_uint32, dp]),
                 "rt_refit_scene": (i32, [dp, sz, C.POINTER(C.c_uint32), sz, fp, vp, sz]),
                 "rt_accel_refit_records": (i32, [C.POINTER(C.c_uint32), sz, i32, vp, sz, vp, sz]),
                 "rt_scene_copy_records": (i32, [vp, i32, C.POINTER(C.c_uint32), sz, C.POINTER(sz)]),

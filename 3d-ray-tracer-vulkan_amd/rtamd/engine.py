@@ -20,8 +20,8 @@ from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._lib import (RT_QUERY_ANY, RT_TEMPORAL_FIXED_SEED, RT_TEMPORAL_RESET, CameraUBO, DenoiseParams, Hit, LearnInfo,
-                   LearnParams, RtError, Stats, TemporalParams, VarianceParams, check, lib)
+from ._lib import (RT_GEOM_F32, RT_QUERY_ANY, RT_TEMPORAL_FIXED_SEED, RT_TEMPORAL_RESET, CameraUBO, DenoiseParams, Hit,
+                   LearnInfo, LearnParams, RtError, Stats, TemporalParams, VarianceParams, check, lib)
 from .scene import BuiltCpuData, Camera
 
 REFERENCE_WIDTH = 1280          # VulkanEngine.java:45
@@ -115,6 +115,47 @@ class Renderer:
         t = C.c_double()
         check(lib().rt_update_geometry(self._ctx, v.ctypes.data, v.nbytes, b.ctypes.data, b.nbytes,
                                        C.byref(t) if ms else None))
+        return t.value if ms else None
+
+    def update_geometry_device(self, tri_verts, source=None, ms: bool = False):
+        """rt_update_geometry_device: update_geometry from a tensor that
+        already lives on the context's device (a one-device context, options
+        "refit" and "refit_device" 1 at the upload).  tri_verts: a contiguous
+        float64 or float32 torch tensor of 9 * n_tris elements (v0, v1, v2 of
+        each input triangle, as build_buffers took them); source: the built
+        scene's flat_source as an int32 tensor on the same device, or None
+        for input that is already in flattened order.  Synchronous: the
+        device is drained first, so whatever stream produced the tensors has
+        finished.  Returns the device time of its kernels in ms with ms=True,
+        else None.  ValueError (before the library is called) for anything
+        but such tensors."""
+        import torch
+        dev = torch.device("cuda", self.device_ids[0])
+
+        def on_device(t, what, dtypes):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{what} must be a torch tensor on {dev}, not {type(t).__name__}")
+            if t.device != dev:
+                raise ValueError(f"{what} is on {t.device}, the context renders on {dev}")
+            if t.dtype not in dtypes:
+                raise ValueError(f"{what} is {t.dtype}, expected one of {[str(d) for d in dtypes]}")
+            if not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous")
+            return t
+
+        tv = on_device(tri_verts, "tri_verts", (torch.float64, torch.float32))
+        if tv.numel() % 9:
+            raise ValueError(f"tri_verts has {tv.numel()} elements, not 9 per triangle")
+        n_tris = tv.numel() // 9
+        if source is None:
+            n_flat, src_ptr = n_tris, None
+        else:
+            src = on_device(source, "source", (torch.int32,))
+            n_flat, src_ptr = src.numel(), src.data_ptr() or None
+        flags = RT_GEOM_F32 if tv.dtype == torch.float32 else 0
+        t = C.c_double()
+        check(lib().rt_update_geometry_device(self._ctx, tv.data_ptr() or None, n_tris, src_ptr, n_flat, flags,
+                                              C.byref(t) if ms else None))
         return t.value if ms else None
 
     def copy_records(self, which: int) -> np.ndarray:
@@ -589,7 +630,8 @@ class HipEngine:
         # variance (True or a VarianceParams): the temporal path with the variance-guided filter
         # (render_temporal's variance=; temporal None = the default parameters).
         # motion: scenes are uploaded with options refit and temporal_motion 1, so that a geometry update
-        # (submit_geometry_update) keeps the temporal history and the next frame reprojects it per triangle.
+        # (submit_geometry_update) keeps the temporal history and the next frame reprojects it per triangle;
+        # refit_device 1 as well, so that the update may come as a tensor on the device.
         self.motion = bool(motion)
         self.denoise = denoise
         self.variance = None if variance is False else variance
@@ -624,13 +666,17 @@ class HipEngine:
     def submit_scene(self, scene_data: BuiltCpuData) -> None:
         self._scene_q.put((scene_data, False))
 
-    def submit_geometry_update(self, built: BuiltCpuData) -> None:
+    def submit_geometry_update(self, built, source=None) -> None:
         """The current scene's triangles moved (rtamd.refit_buffers of the
         submitted scene): queued like a scene and applied on the render thread
         through Renderer.update_geometry, after the frames in flight.  The
         engine must have been made with motion=True, which uploads scenes with
-        the refit tables."""
-        self._scene_q.put((built, True))
+        the refit tables.  built may also be a torch tensor of the moved input
+        triangles on the engine's device (with source, the scene's flat_source
+        as an int32 tensor there, or None for flattened order): applied
+        through Renderer.update_geometry_device; the caller keeps both tensors
+        unchanged until the update has been applied (geometry_updates)."""
+        self._scene_q.put((built if isinstance(built, BuiltCpuData) else (built, source), True))
 
     def submit_camera_update(self, camera: Camera) -> None:
         self._camera_q.put(camera)
@@ -647,6 +693,7 @@ class HipEngine:
             renderer.set_option("async_slots", self.inflight)
             if self.motion:
                 renderer.set_option("refit", 1)
+                renderer.set_option("refit_device", 1)
                 renderer.set_option("temporal_motion", 1)
             have_scene, camera = False, None
             while self._running:
@@ -655,7 +702,10 @@ class HipEngine:
                     while pending:                          # frames of the old scene first
                         self._finish(renderer, slots, pending.pop(0))
                     if update:
-                        renderer.update_geometry(scene)
+                        if isinstance(scene, BuiltCpuData):
+                            renderer.update_geometry(scene)
+                        else:
+                            renderer.update_geometry_device(*scene)
                         self.geometry_updates += 1
                     else:
                         renderer.upload_scene(scene)

@@ -296,6 +296,41 @@ int rt_render_poll(rt_ctx* ctx, uint64_t ticket, int* done);
 int rt_update_geometry(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
                        const void* bvh_nodes, size_t bvh_bytes, double* ms);
 
+/* rt_update_geometry from device memory: rt_refit_scene
+ * restated on the device, then rt_update_geometry's own stages.  Needs a
+ * one-device context and a scene uploaded with options "refit" and
+ * "refit_device" 1.  Added at ABI version 6 without a bump.
+ *
+ * d_tri_verts: a DEVICE pointer on the context's device to n_tris * 9 doubles
+ *            (floats with RT_GEOM_F32, widened to double exactly), laid out as
+ *            rt_refit_scene's tri_verts; aligned to its element size, never
+ *            written.  May be NULL only with n_tris 0.
+ * d_source : a DEVICE pointer to n_flat entries: flattened triangle f copies
+ *            input triangle d_source[f] (rt_build_scene_map's out_source).
+ *            NULL: the input lies in flattened order, and n_tris == n_flat.
+ * n_flat   : the uploaded scene's flattened triangle count.
+ * Afterwards every device array of the scene, and so every frame, query,
+ * first-hit buffer, pick and work counter, is bit for bit what
+ * rt_refit_scene(tri_verts as doubles, source, ...) on the uploaded nodes
+ * followed by rt_update_geometry leaves on the same context, and everything
+ * rt_update_geometry promises (history, samples sum, "temporal_motion",
+ * learned orders) holds.  Synchronous: it first waits for the device (which
+ * also completes the stream that produced the input) and returns with the
+ * update done.  ms (nullable): the device time of all its kernels (HIP events).
+ * Errors, the scene and the staging arrays unchanged in every case:
+ * RT_ERR_NO_SCENE; RT_ERR_INVALID_ARG for a null context or input, unknown
+ * flag bits, a misaligned pointer, a pointer that is not memory of the
+ * context's device or whose allocation is too small, n_flat that is not the
+ * scene's, d_source NULL with n_tris != n_flat, n_tris 0 for a scene with
+ * triangles, a context of several devices, or a scene without the device
+ * tables (option "refit_device"); RT_ERR_BAD_SCENE (the message names the
+ * lowest offending flattened triangle) for a d_source entry >= n_tris, a
+ * vertex whose float cast is not finite, or a dropped duplicate as in
+ * rt_update_geometry.  An empty scene stays empty: RT_OK. */
+#define RT_GEOM_F32 1   /* flags: d_tri_verts holds floats (widened to double exactly), else doubles */
+int rt_update_geometry_device(rt_ctx* ctx, const void* d_tri_verts, size_t n_tris,
+                              const uint32_t* d_source, size_t n_flat, uint32_t flags, double* ms);
+
 /* The two buffers rt_update_geometry takes, from moved input triangles (pure
  * host code).  tri_verts: n_tris*9 doubles as rt_build_scene_map took them;
  * source: its out_source (n_flat entries); out_vertices: n_flat*12 floats;
@@ -1085,6 +1120,17 @@ int rt_render_samples(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int heig
  *                   tables.  0 / 1
  *   "refit_used"    (rt_get_option only) 1 when the current scene holds them
  *   "refit_bytes"   (rt_get_option only) the device bytes they take on device 0
+ *   "refit_device"  at the next rt_upload_scene, with "refit" 1 and a scene that
+ *                   holds the refit tables: 1 = keep on the device what
+ *                   rt_update_geometry_device needs as well: the reference
+ *                   nodes of the root's subtree grouped by height (4 B per
+ *                   node; the level offsets stay on the host), the (dropped,
+ *                   kept) duplicate pairs with their leaves (16 B per pair) and
+ *                   16 B of status ("refit_bytes" includes them).  No double
+ *                   boxes are kept.  A reference tree of more
+ *                   than 1024 levels (a hand-made chain) gets none: one launch
+ *                   per level.  0 (default) = an upload is what it was.  0 / 1
+ *   "refit_device_used" (rt_get_option only) 1 when the current scene holds them
  *   "plain_kernels" (rt_get_option only) production-build trace kernels enqueued
  *                   on device 0 so far (not counting, diagnostic or learning
  *                   launches, nor query launches): lets a profiler's kernel trace be cut at a

@@ -19,6 +19,21 @@ stream, device events, windows of --frames frames) before and after an
 identity update: the records are byte-identical, so the two must agree within
 the windows' own spread.
 
+--device (needs a GPU): rt_update_geometry_device beside the
+path it replaces, for each config, in one process, the same translated cube,
+the median of --calls calls after one warm-up of each, alternating between the
+moved and the original triangles:
+
+  old_wall_ms      host wall time of rt_refit_scene (rtamd.refit_buffers) followed
+                   by rt_update_geometry from pageable memory; old_refit_scene_ms
+                   and old_update_wall_ms are its two parts, old_update_ms the
+                   update's `ms`
+  device_wall_ms   host wall time of rt_update_geometry_device on a float64
+                   tensor (and the source map) already resident on the device
+  device_ms        its `ms`: the device time of all its kernels
+  same_records     every device array after the last device update equals the
+                   arrays after the host path's update of the same triangles
+
 --quality (CPU only): node visits per segment of the accel walk's CPU model
 (oracle/rt_accel_model.c) over config 3 after deformations (b), (c) and (f),
 on the refitted records and on a fresh rt_accel_records of the moved scene:
@@ -131,6 +146,68 @@ def bench_config(k, args):
         emit(rec, args.out)
 
 
+def bench_device(k, args):
+    import numpy as np
+    import rtamd
+    import torch
+    from rtamd import build_buffers, configs, refit_buffers, triangles_of
+    cfg = configs.get(k)
+    tv, mats = triangles_of(cfg.scene)
+    tv = np.ascontiguousarray(tv, dtype=np.float64).reshape(-1, 9)
+    built = build_buffers(tv, mats, 1)
+    states = [moved_cube(tv), tv]
+    with rtamd.Renderer((0,)) as r:
+        r.set_option("accel", args.accel)
+        r.set_option("refit", 1)
+        r.upload_scene(built)
+        plain_bytes = r.get_option("refit_bytes")
+        r.set_option("refit_device", 1)
+        r.upload_scene(built)
+        assert r.get_option("refit_device_used") == 1
+        rec = {"what": "device_vs_host_update", "config": k, "accel_used": r.get_option("accel_used"),
+               "flat_triangles": built.triangle_count, "nodes": built.n_nodes, "input_triangles": len(tv),
+               "refit_bytes": r.get_option("refit_bytes"), "refit_device_bytes": r.get_option("refit_bytes") - plain_bytes,
+               "calls": args.calls}
+        # the old path: rt_refit_scene on one host thread, then the update from pageable memory
+        r.update_geometry(refit_buffers(built, states[0]))
+        refit_ms, upd_ms, old_ms, old_dev = [], [], [], []
+        for i in range(args.calls):
+            t0 = time.perf_counter()
+            new = refit_buffers(built, states[(i + 1) % 2])
+            t1 = time.perf_counter()
+            old_dev.append(r.update_geometry(new, ms=True))
+            t2 = time.perf_counter()
+            refit_ms.append((t1 - t0) * 1e3)
+            upd_ms.append((t2 - t1) * 1e3)
+            old_ms.append((t2 - t0) * 1e3)
+        last = (args.calls) % 2                  # the state the last call left
+        want = [r.copy_records(w) for w in range(6)]
+        # the new path: the triangles and the source map already live on the device
+        d_states = [torch.from_numpy(x).cuda() for x in states]
+        d_src = torch.from_numpy(np.asarray(built.flat_source).astype(np.int32)).cuda()
+        torch.cuda.synchronize()
+        r.update_geometry_device(d_states[0], d_src)
+        wall, dev = [], []
+        for i in range(args.calls):
+            t0 = time.perf_counter()
+            ms = r.update_geometry_device(d_states[(i + 1) % 2], d_src, ms=True)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            dev.append(ms)
+        same = all(np.array_equal(r.copy_records(w), want[w]) for w in range(6))
+        med = statistics.median
+
+        def mm(x, nd=3):
+            return [round(min(x), nd), round(max(x), nd)]
+        rec.update({"old_wall_ms": round(med(old_ms), 3), "old_wall_min_max_ms": mm(old_ms),
+                    "old_refit_scene_ms": round(med(refit_ms), 3), "old_update_wall_ms": round(med(upd_ms), 3),
+                    "old_update_ms": round(med(old_dev), 4),
+                    "device_wall_ms": round(med(wall), 3), "device_wall_min_max_ms": mm(wall),
+                    "device_ms": round(med(dev), 4), "device_ms_min_max": mm(dev, 4),
+                    "last_state": last, "same_records": bool(same)})
+        rec["ratio"] = round(rec["old_wall_ms"] / rec["device_wall_ms"], 1)
+        emit(rec, args.out)
+
+
 def quality(args):
     import numpy as np
     import refit_ref as R
@@ -172,6 +249,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--accel", type=int, default=8)
     ap.add_argument("--quality", action="store_true")
+    ap.add_argument("--device", action="store_true", help="time rt_update_geometry_device beside the host path")
     ap.add_argument("--row-step", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refit", "refit_bench.jsonl"))
     args = ap.parse_args()
@@ -184,7 +262,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("refit_bench.py needs a GPU for the timings (--quality runs without one)")
     for k in (int(x) for x in args.configs.split(",")):
-        bench_config(k, args)
+        (bench_device if args.device else bench_config)(k, args)
 
 
 if __name__ == "__main__":
