@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/rtamd.h"
+#include "rng_table_host.h"
 
 namespace rtamd {
 
@@ -219,6 +220,13 @@ struct TraceArgs {
     float*   out_lin = nullptr; // when set, the end of a path stores its linear colour (finish_pixel's fin,
                                 //   before the sqrt) as 3 floats where out_rad would put the pixel, and
                                 //   neither out_rgba nor out_rad is written
+    // The table of scatter draws (option rng_table; rng_table_host.h): rng_k planes of width x height
+    // float4 entries, read by the kFeatRng kernels only, which a launch takes exactly when rng_k > 0.  Below
+    // bounce rng_k such a path keeps its first seed y * width + x, which indexes every plane, where the other
+    // kernels keep the running seed; the entry read at bounce rng_k - 1 hands over the running seed.
+    // Behind every field the other kernels read, like the fields above.
+    const float4* rng_table = nullptr;
+    int      rng_k = 0;
 };
 
 // Host-side compact-scene build from the reference records; validates the
@@ -290,6 +298,10 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels = n
 hipError_t launch_query(const TraceArgs& a, hipStream_t stream);
 
 void set_error(const char* fmt, ...);
+
+// rt_rngtable.hip: enqueues the kernel that fills the table of scatter draws (rng_table_host.h:
+// rng_table_bytes(width, height, k) bytes at `table`) on `stream`.
+hipError_t launch_rng_table(float4* table, int width, int height, int k, hipStream_t stream);
 
 // rt_wire.hip: the RGB wire format of the multi-GPU exchange (n_px pixels;
 // rgba 16-B aligned, rgb 4-B aligned).

@@ -317,6 +317,13 @@ struct PerDevice {
     struct Slots { hipStream_t s; char* base; size_t bytes; };
     std::vector<Slots> slots;
     int          last_split = 0;    // the bounce the last launch split at (option "split_bounce_used", read only)
+    // option rng_table (rt_rng.h): the device's table of scatter draws, complete before
+    // attach_rng returns from building it, for frames of rng_w x rng_h and rng_k bounces; a size that did
+    // not fit the device is remembered (rng_oom_*) and not tried again
+    float4*      d_rng = nullptr;
+    int          rng_w = 0, rng_h = 0, rng_k = 0;
+    int          rng_oom_w = 0, rng_oom_h = 0, rng_oom_k = 0;
+    int          last_rng = 0;      // the table's bounces the last launch read (option "rng_table_used", read only)
     // queries (rt_query_rays, rt_pick): the host forms' device staging, rays
     // then hits, grown to the largest batch; and L(0) of the reference's own
     // tree, which a query over an accel scene's reference records starts from
@@ -380,6 +387,12 @@ static constexpr size_t kSplitSlotBytes = 256ull << 20;
 // (0.1153-0.1157 against 0.1121-0.1125, 0.1344-0.1369 against 0.1174-0.1194;
 // profiles/split)
 static constexpr int kSplitPixelsDefault = 6000000;
+// options rng_table / rng_table_mb's defaults (profiles/rng_table)
+static constexpr int kRngTableDefault = 2;
+static constexpr int kRngTableMbDefault = 512;
+// option rng_table_pixels' default: launches of 4 frames of 1920x1080 measured 3.2% faster with the table
+// (config 3; one 3840x2160 frame: even), launches of 1 frame 8% slower (profiles/rng_table)
+static constexpr int kRngTablePixelsDefault = 8000000;
 // The walk's buffer loads address the records with 32-bit byte offsets
 // (rt_trace.hip wbuf): at most 2^27 - 4 slots of 32 B (~45M triangles).
 static constexpr unsigned kMaxWalkSlots = (1u << 27) - 4;
@@ -494,6 +507,14 @@ struct rt_ctx {
     int  split_capacity = 64;      // split launch: the queues' entries together, per 1024 pixels of the
                                    //   launch (survivors of bounce 2: 27 per 1024 on config 3; 0 = none:
                                    //   every wave keeps its paths)
+    int  rng_table = kRngTableDefault;   // format-0 accel launches without tail or extensions: the first this-many
+                                   //   bounces read their rnd_in_sphere point from a per-resolution table
+                                   //   (0 = every draw is computed)
+    int  rng_table_pixels = kRngTablePixelsDefault;   // only launches of at least this many pixels (all their frames
+                                   //   together) read the table: a small launch is bound by its waves' latency,
+                                   //   to which the table's load adds
+    int  rng_table_mb = kRngTableMbDefault;   // the most memory (MiB) a device's table may take: a larger one is
+                                   //   not built and the launch computes its draws
     // At the next upload: 0 = the reference's tree and order; 1 / 8 = the
     // binned-SAH tree in 1 / 8 (octant) layouts (accel_build.h).
     // Config 3 0.1279-0.1288 ms per frame against 0.2962-0.2964 for the
@@ -1064,7 +1085,7 @@ static std::vector<uint64_t> launch_key(const TraceArgs& a, hipStream_t s) {
             (uint64_t)a.heavy_tiles, (uint64_t)(a.aux_stream != nullptr), (uint64_t)a.heavy_fused, P(a.heavy_px),
             (uint64_t)a.n_heavy_px, P(a.tile_mask), (uint64_t)a.coop_walk, (uint64_t)a.coop_win,
             (uint64_t)a.split_bounce, P(a.q_slots), (uint64_t)a.q_queues, (uint64_t)a.q_cap,
-            (uint64_t)a.sample_step, P(a.out_lin)};
+            (uint64_t)a.sample_step, P(a.out_lin), P(a.rng_table), (uint64_t)a.rng_k};
     for (int f = 0; f < a.n_frames; ++f) {
         const CamF& c = a.cams[f];
         for (float v : {c.ox, c.oy, c.oz, c.lx, c.ly, c.lz, c.hx, c.hy, c.hz, c.vx, c.vy, c.vz}) k.push_back(F(v));
@@ -1138,9 +1159,64 @@ static int attach_slots(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, hipStream
     return RT_OK;
 }
 
+// Option rng_table: whether this launch reads its scatter draws from the device's table, and
+// the table for it.  The table is keyed by the full frame's width and height (what a seed is formed from)
+// and the option's K, whatever part of the frame the launch covers.
+//
+// Ordering against the launch streams, which run several launches at once: the build enqueues the fill
+// kernel on this launch's stream and waits for it on the host before it returns, so every launch that is
+// handed the table, on whichever stream, is enqueued after the table is complete, and a launch carries no
+// wait of its own.  A table of another size first waits for the whole device: launches still queued on
+// any stream may read the old one.
+static int attach_rng(const rt_ctx* ctx, PerDevice& p, TraceArgs& a, hipStream_t s) {
+    a.rng_table = nullptr;
+    a.rng_k = 0;
+    // what launch_trace has kFeatRng kernels for: a production or counting launch over format-0 accel
+    // records without a cooperative tail.  (An extension launch changes the seed per frame.)
+    if (ctx->rng_table <= 0 || !p.scene.n_layouts || p.scene.half || p.scene.wide || a.coop_lanes > 0 || a.ext ||
+        a.diag || a.walk != 2 || a.max_bounces < 1)
+        return RT_OK;
+    if ((long long)a.tw * a.th * a.n_frames < ctx->rng_table_pixels) return RT_OK;
+    const int k = ctx->rng_table;
+    const uint64_t bytes = rng_table_bytes(a.width, a.height, k);
+    if (!rng_table_fits(bytes, ctx->rng_table_mb)) return RT_OK;
+    if (!(p.d_rng && p.rng_w == a.width && p.rng_h == a.height && p.rng_k == k)) {
+        if (p.rng_oom_w == a.width && p.rng_oom_h == a.height && p.rng_oom_k == k) return RT_OK;
+        if (p.d_rng) {
+            RT_HIP_CHECK(hipDeviceSynchronize());
+            (void)hipFree(p.d_rng);
+            p.d_rng = nullptr;
+            p.rng_w = p.rng_h = p.rng_k = 0;
+        }
+        void* base = nullptr;
+        if (hipMalloc(&base, (size_t)bytes) != hipSuccess) {
+            (void)hipGetLastError();                        // no room: this size computes its draws
+            p.rng_oom_w = a.width;
+            p.rng_oom_h = a.height;
+            p.rng_oom_k = k;
+            return RT_OK;
+        }
+        hipError_t e = launch_rng_table(static_cast<float4*>(base), a.width, a.height, k, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(base);
+            RT_HIP_CHECK(e);
+        }
+        p.d_rng = static_cast<float4*>(base);
+        p.rng_w = a.width;
+        p.rng_h = a.height;
+        p.rng_k = k;
+    }
+    a.rng_table = p.d_rng;
+    a.rng_k = k;
+    return RT_OK;
+}
+
 static int launch(const rt_ctx* ctx, PerDevice& p, const TraceArgs& a_in, hipStream_t s) {
     TraceArgs a = a_in;
     if (int rq = attach_slots(ctx, p, a, s)) return rq;
+    if (int rr = attach_rng(ctx, p, a, s)) return rr;
+    p.last_rng = a.rng_k;
     // Only a frame of two launches (heavy tiles on an auxiliary stream,
     // heavy_stream 1) gains from a graph: its fork and join become edges.  A
     // single launch (the fused heavy tiles, or none) goes straight to the
@@ -1404,6 +1480,7 @@ int rt_destroy(rt_ctx* ctx) {
         p.slots.clear();
         if (p.d_accum) (void)hipFree(p.d_accum);
         if (p.d_spheres) (void)hipFree(p.d_spheres);
+        if (p.d_rng) (void)hipFree(p.d_rng);
         if (p.d_query) (void)hipFree(p.d_query);
         if (p.d_denoise) (void)hipFree(p.d_denoise);
         if (p.d_temporal) (void)hipFree(p.d_temporal);
@@ -3520,6 +3597,9 @@ static const Option kOptions[] = {
     in_range("split_pixels", &rt_ctx::split_pixels, 0, 1 << 30),
     in_range("split_queues", &rt_ctx::split_queues, 1, kMaxSplitQueues),
     in_range("split_capacity", &rt_ctx::split_capacity, 0, 1024),
+    in_range("rng_table", &rt_ctx::rng_table, 0, kRngTableMaxK),
+    in_range("rng_table_mb", &rt_ctx::rng_table_mb, 0, kRngTableMaxMb),
+    in_range("rng_table_pixels", &rt_ctx::rng_table_pixels, 0, 1 << 30),
     in_range("heavy_stream", &rt_ctx::heavy_stream, 0, 2),
     one_of("graph", &rt_ctx::graph, 0, 1),
     one_of("diag", &rt_ctx::diag, 0, 1),
@@ -3588,6 +3668,7 @@ int rt_get_option(rt_ctx* ctx, const char* name, int64_t* value) {
     else if (is("solo_lanes_used")) *value = p ? p->last_solo : 0;
     else if (is("plain_kernels")) *value = p ? (int64_t)p->plain_kernels : 0;
     else if (is("split_bounce_used")) *value = p ? p->last_split : 0;
+    else if (is("rng_table_used")) *value = p ? p->last_rng : 0;
     else if (is("split_overflow")) {
         // diagnostic: waits for every device, then reads and zeroes each
         // launch stream's count of kernel-1 waves whose claim did not fit
@@ -3696,6 +3777,39 @@ int rt_learn_copy(rt_ctx* ctx, rt_learn_info* info, int32_t* order, uint64_t* ma
         RT_HIP_CHECK(hipMemcpy(records, p.d_learn + (size_t)o.given.rec_off * kDiagWords,
                                o.n * kDiagWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (lanes) RT_HIP_CHECK(hipMemcpy(lanes, p.d_learn_lane, o.n * 64 * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_rng_table_bytes(int width, int height, int k, uint64_t* bytes) {
+    if (!bytes) { set_error("rt_rng_table_bytes: null argument"); return RT_ERR_INVALID_ARG; }
+    *bytes = rng_table_bytes(width, height, k);
+    return RT_OK;
+}
+
+int rt_rng_table_copy(rt_ctx* ctx, void* dst, size_t cap_bytes, int* width, int* height, int* k) {
+    if (!ctx || ctx->dev.empty()) { set_error("rt_rng_table_copy: null context"); return RT_ERR_INVALID_ARG; }
+    PerDevice& p = ctx->dev[0];
+    if (width) *width = p.rng_w;
+    if (height) *height = p.rng_h;
+    if (k) *k = p.rng_k;
+    if (dst && p.d_rng) {
+        RT_HIP_CHECK(hipSetDevice(p.device));
+        RT_HIP_CHECK(hipDeviceSynchronize());
+        const size_t n = (size_t)std::min<uint64_t>(cap_bytes, rng_table_bytes(p.rng_w, p.rng_h, p.rng_k));
+        RT_HIP_CHECK(hipMemcpy(dst, p.d_rng, n, hipMemcpyDeviceToHost));
+    }
+    return RT_OK;
+}
+
+int rt_rng_table_launch_key(const void* table, int k, uint64_t* key, size_t cap, size_t* n) {
+    if (!n || (cap && !key)) { set_error("rt_rng_table_launch_key: null argument"); return RT_ERR_INVALID_ARG; }
+    TraceArgs a;
+    a.n_frames = 1;
+    a.rng_table = static_cast<const float4*>(table);
+    a.rng_k = k;
+    const std::vector<uint64_t> v = launch_key(a, nullptr);
+    *n = v.size();
+    for (size_t i = 0; i < std::min(cap, v.size()); ++i) key[i] = v[i];
     return RT_OK;
 }
 

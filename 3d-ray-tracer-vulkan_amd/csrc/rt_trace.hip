@@ -41,6 +41,7 @@
 
 #include "rt_internal.h"
 #include "rt_pixel.h"
+#include "rt_rng.h"
 
 namespace rtamd {
 
@@ -48,46 +49,18 @@ namespace {
 
 constexpr float kTMin = 0.001f;              // compute_dynamic_ray.comp:42
 constexpr float kTMax = 10000.0f;            // :43
-constexpr int   kMaxRejectTriples = 1 << 16; // bound on the rejection loop (:65-68), see DESIGN.md
-
-struct V3 { float x, y, z; };
+// (V3, vdot and the random numbers, pcg / rnd / rnd_in_sphere: rt_rng.h)
 
 __device__ __forceinline__ V3 vadd(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
 __device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ V3 vmul(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
 __device__ __forceinline__ V3 vscale(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float vdot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ V3 vcross(V3 a, V3 b) {
     return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
 __device__ __forceinline__ V3 vnormalize(V3 a) {
     const float l = sqrtf(vdot(a, a));
     return {a.x / l, a.y / l, a.z / l};
-}
-
-// pcg (compute_dynamic_ray.comp:52-56) and randomFloat (:58-61).
-__device__ __forceinline__ uint32_t pcg(uint32_t v) {
-    const uint32_t s = v * 747796405u + 2891336453u;
-    const uint32_t w = ((s >> ((s >> 28u) + 4u)) ^ s) * 277803737u;
-    return (w >> 22u) ^ w;
-}
-__device__ __forceinline__ float rnd(uint32_t& seed) {
-    seed = pcg(seed);
-    return (float)seed / 4294967296.0f;   // float(0xFFFFFFFFu) rounds to 2^32
-}
-
-// randomVec3InUnitSphere (:63-70): three draws are made and discarded, then
-// rejection sampling of 2*rand3-1 until dot(p,p) < 1.
-__device__ __forceinline__ V3 rnd_in_sphere(uint32_t& seed) {
-    seed = pcg(pcg(pcg(seed)));
-    for (int it = 0; it < kMaxRejectTriples; ++it) {
-        const float a = rnd(seed);
-        const float b = rnd(seed);
-        const float c = rnd(seed);
-        const V3 p = {a * 2.0f - 1.0f, b * 2.0f - 1.0f, c * 2.0f - 1.0f};
-        if (vdot(p, p) < 1.0f) return p;
-    }
-    return {0.0f, 0.0f, 0.0f};
 }
 
 // Frame row of local row ly of frame f of the launch (rt_internal.h, TraceArgs
@@ -268,6 +241,28 @@ __device__ __forceinline__ bool scatter(float4 M, V3 d, V3 n, uint32_t& seed, V3
         const float k = 2.0f * vdot(n, di);
         const V3 refl = vsub(di, vscale(n, k));                           // reflect()
         const V3 p = rnd_in_sphere(seed);
+        nd = vnormalize(vadd(refl, vscale(p, fuzz)));
+        return vdot(nd, n) > 0.0f;
+    }
+    nd = d;
+    return false;                                                         // :153
+}
+
+// scatter with the bounce's rnd_in_sphere point handed in (the kFeatRng kernels: the point is a table entry
+// or the call's result, one value for both arms).  The arithmetic is scatter's.
+__device__ __forceinline__ bool scatter_at(float4 M, V3 d, V3 n, V3 p, V3& nd) {
+    if (M.w == 0.0f) {                                                    // Lambertian :137-143
+        const V3 ru = vnormalize(p);
+        V3 sd = vadd(n, ru);
+        if (sqrtf(vdot(sd, sd)) < 0.0001f) sd = n;
+        nd = vnormalize(sd);
+        return true;
+    }
+    if (M.w == 1.0f || M.w == 2.0f) {                                     // metal :145-151
+        const float fuzz = (M.w == 2.0f) ? 0.3f : 0.0f;
+        const V3 di = vnormalize(d);
+        const float k = 2.0f * vdot(n, di);
+        const V3 refl = vsub(di, vscale(n, k));                           // reflect()
         nd = vnormalize(vadd(refl, vscale(p, fuzz)));
         return vdot(nd, n) > 0.0f;
     }
@@ -905,6 +900,9 @@ constexpr int kFeatQuery = 16384; // query mode (launch_query): 
                                   //   from its own t_max, and its hit record is stored instead of shading
 constexpr int kFeatSolo = 32768;  // option solo_lanes (with kFeatAccel, format 0, no cooperative tail): the
                                   //   last solo_lanes walks of a wave run in solo_walk's scalar loop
+constexpr int kFeatRng = 65536;   // option rng_table (with kFeatAccel, format 0, no cooperative tail, no
+                                  //   extensions): below bounce TraceArgs::rng_k a bounce's rnd_in_sphere point
+                                  //   is one 16-B load from the table of scatter draws
 constexpr unsigned kHeavyLaneMark = kLearnHeavyMark;   // rt_internal.h
 
 // A query's hit record (rtamd.h rt_hit): (t, tri, normal.xy), (normal.z, pos.xyz).
@@ -1099,6 +1097,12 @@ void trace_simple(TraceArgs a) {
     constexpr bool SOLO = (FEAT & kFeatSolo) != 0;
     static_assert(!SOLO || (ACC && !HALF && !WIDE && WALK == 2 && !(FEAT & (kFeatCoopTail | kFeatExt))),
                   "kFeatSolo goes with the format-0 accel walk alone");
+    // the table of scatter draws: the same kernels, with or without the solo walk; never a query, a
+    // diagnostic launch or an extension build (whose seeds change per frame)
+    constexpr bool RNG = (FEAT & kFeatRng) != 0;
+    static_assert(!RNG || (ACC && !HALF && !WIDE && WALK == 2 && !DIAG &&
+                           !(FEAT & (kFeatCoopTail | kFeatExt | kFeatQuery | kFeatFused))),
+                  "kFeatRng goes with the format-0 accel walk's frame kernels alone");
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     // frontier_walk's per-wave frontiers (kFCap entries per wave; dynamic LDS,
@@ -1281,10 +1285,19 @@ void trace_simple(TraceArgs a) {
             seed = (uint32_t)(y * a.width + x) +
                    (uint32_t)(a.frame_count + fr_i * a.sample_step) * (uint32_t)(a.width * a.height);
             primary_ray_seeded(a, fr_i, x, y, seed, o, d);
+        } else if (RNG) {
+            // below bounce rng_k the lane's seed register holds the first seed, the index of its table
+            // entries: the primary ray's two draws run on a copy
+            seed = (uint32_t)(y * a.width + x);
+            uint32_t js = seed;
+            primary_ray_seeded(a, fr_i, x, y, js, o, d);
+            if (a.rng_k <= 0) seed = js;
         } else {
             primary_ray(a, fr_i, x, y, seed, o, d);
         }
     }
+    // RNG: the table's planes, one buffer resource per bounce over that plane alone (rng_table_host.h)
+    const unsigned rng_plane = RNG ? (unsigned)(a.width * a.height) * 16u : 0u;   // bytes (<= 2^31)
 
     // The bounce loop (:179) is wave-uniform: a lane whose path has ended
     // stays in it with alive = false, so the cooperative tail below can use
@@ -1706,10 +1719,35 @@ void trace_simple(TraceArgs a) {
                     M = a.scene.mats[kShadeStride * hit];
                 }
                 V3 nd;
+                bool scattered = false;
+                if (RNG) {
+                    V3 pt;
+                    if (b < a.rng_k) {
+                        // Below bounce rng_k (wave-uniform) the bounce's rnd_in_sphere point is a 12-B
+                        // load, requested here, behind the normal and material loads, so that the three
+                        // are in flight together; non-temporal, so that it does not evict walk records
+                        // from L2.  At the table's last bounce the entry's .w, the running seed, is
+                        // loaded over the first seed in the lane's seed register.  (One 16-B load
+                        // requested ahead of the other two took four more registers there: the compiler
+                        // waited for it at once and spilled it.)  The plane is a buffer resource of its
+                        // own: an offset outside it reads zeros
+                        const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
+                            reinterpret_cast<char*>(const_cast<float4*>(a.rng_table)) + (size_t)b * rng_plane, 0,
+                            (int)rng_plane, 0x00020000);
+                        const int eo = (int)(seed << 4);
+                        const auto v = __builtin_amdgcn_raw_buffer_load_b96(prs, eo, 0, 2 /* nt */);
+                        if (b == a.rng_k - 1)
+                            seed = __builtin_amdgcn_raw_buffer_load_b32(prs, eo + 12, 0, 2 /* nt */);
+                        pt = {__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2])};
+                    } else {
+                        pt = rnd_in_sphere(seed);
+                    }
+                    scattered = scatter_at(M, d, nrm, pt, nd);
+                }
                 if ((FEAT & kFeatExt) && (a.ext & kExtEmissive) && M.w == 3.0f) {
                     fin = vmul(att, V3{M.x, M.y, M.z});                   // extension: type 3 emits
                     alive = false;
-                } else if (!scatter(M, d, nrm, seed, nd)) {
+                } else if (RNG ? !scattered : !scatter(M, d, nrm, seed, nd)) {
                     alive = false;                                        // attenuation = 0: black
                 } else {
                     att = vmul(att, V3{M.x, M.y, M.z});
@@ -1854,6 +1892,14 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels) {
     if (a.diag) hipLaunchKernelGGL((trace_simple<false, true, F, W>), grid, block, RT_SHM(F), stream, ao);           \
     else if (a.counters) hipLaunchKernelGGL((trace_simple<true, false, F, W>), grid, block, RT_SHM(F), stream, ao); \
     else hipLaunchKernelGGL((trace_simple<false, false, F, W>), grid, block, RT_SHM(F), stream, ao);
+#define RT_RNG(F)                                                                                               \
+    if (a.counters) hipLaunchKernelGGL((trace_simple<true, false, F, 2>), grid, block, 0, stream, ao);            \
+    else hipLaunchKernelGGL((trace_simple<false, false, F, 2>), grid, block, 0, stream, ao);
+    if (a.rng_k > 0 && (!a.rng_table || a.scene.n_layouts == 0 || a.scene.half || a.scene.wide || feat != 0 ||
+                        a.diag)) {
+        set_error("launch with a table of scatter draws that its kernel does not read");   // attach_rng never asks
+        return hipErrorInvalidValue;
+    }
     if (a.scene.n_layouts > 0) {
         // option accel (walk 2 records; the launcher never splits heavy tiles
         // or pixels out of an accel launch, and there is no frontier tail)
@@ -1862,7 +1908,15 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels) {
             !a.diag && !a.counters && a.q_queues > 0 && a.q_packs > 0) {
             // split launch: kernel 1 to bounce split_bounce,
             // kernel 2 for the queued paths, both on the launch's stream
-            if (a.solo_lanes > 0)
+            // (rng_k > 0: the kFeatRng builds of both kernels; an entry's seed word is then the first seed
+            // while split_bounce < rng_k, and kernel 2 reads it the same way)
+            if (a.rng_k > 0 && a.solo_lanes > 0)
+                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ1 | kFeatSolo | kFeatRng, 2>), grid,
+                                   block, 0, stream, ao);
+            else if (a.rng_k > 0)
+                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ1 | kFeatRng, 2>), grid, block, 0,
+                                   stream, ao);
+            else if (a.solo_lanes > 0)
                 hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ1 | kFeatSolo, 2>), grid, block, 0,
                                    stream, ao);
             else
@@ -1872,7 +1926,16 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels) {
             a2.split_n = 0;
             a2.block_waves = 1;
             const dim3 grid2((unsigned)a.q_queues * (unsigned)a.q_packs);
-            if (a.solo_lanes > 0)
+            // (kernel 2 starts at bounce split_bounce: where the table ends at or before it, the entries
+            // carry running seeds and kernel 2 is the build without the table)
+            const bool rng2 = a.rng_k > a.split_bounce;
+            if (rng2 && a.solo_lanes > 0)
+                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ2 | kFeatSolo | kFeatRng, 2>), grid2,
+                                   dim3(64), 0, stream, a2);
+            else if (rng2)
+                hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ2 | kFeatRng, 2>), grid2, dim3(64), 0,
+                                   stream, a2);
+            else if (a.solo_lanes > 0)
                 hipLaunchKernelGGL((trace_simple<false, false, kFeatAccel | kFeatQ2 | kFeatSolo, 2>), grid2,
                                    dim3(64), 0, stream, a2);
             else
@@ -1908,7 +1971,12 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels) {
                 break;
             case 0:
                 // (solo_lanes > 0 only where set_schedule allows it: format 0, no tail, no extensions)
-                if (a.solo_lanes > 0) RT_SIMPLE(kFeatAccel | kFeatSolo, 2)
+                // (rng_k > 0, never with diagnostics: the production and counting builds with kFeatRng)
+                if (a.rng_k > 0 && !a.diag) {
+                    if (a.solo_lanes > 0) RT_RNG(kFeatAccel | kFeatSolo | kFeatRng)
+                    else RT_RNG(kFeatAccel | kFeatRng)
+                }
+                else if (a.solo_lanes > 0) RT_SIMPLE(kFeatAccel | kFeatSolo, 2)
                 else RT_SIMPLE(kFeatAccel, 2)
                 break;
             default: RT_SIMPLE(kFeatCoopTail | kFeatExt | kFeatAccel, 2) break;
@@ -1933,6 +2001,7 @@ hipError_t launch_trace(const TraceArgs& a, hipStream_t stream, int* kernels) {
             default: RT_SIMPLE(kFeatCoopTail | kFeatExt | kFeatFrontier, 0) break;
         }
     }
+#undef RT_RNG
 #undef RT_SIMPLE
 #undef RT_SHM
 #undef RT_FUSED_BIG

@@ -48,14 +48,16 @@ EXPORTED = (
     "rt_samples_workspace_bytes", "rt_render_samples_device", "rt_render_samples",
     "rt_update_geometry", "rt_refit_scene", "rt_accel_refit_records", "rt_scene_copy_records",
     "rt_update_geometry_device",
+    "rt_rng_table_bytes", "rt_rng_table_copy", "rt_rng_table_launch_key",
 )
 
 # The library's sources in the Makefile's SRC_ALL order: rt_build_id's
 # "src=" field is the first 16 hex digits of SHA-256 over them concatenated.
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
-                 "csrc/rt_filter.hip", "csrc/rt_temporal.hip", "csrc/rt_samples.hip", "csrc/rt_refit.hip",
+                 "csrc/rt_filter.hip", "csrc/rt_temporal.hip", "csrc/rt_samples.hip", "csrc/rt_refit.hip", "csrc/rt_rngtable.hip",
                  "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h", "csrc/rt_pixel.h",
-                 "csrc/accel_build.h", "csrc/temporal_motion_host.h", "csrc/refit_levels_host.h", "../include/rtamd.h")
+                 "csrc/accel_build.h", "csrc/temporal_motion_host.h", "csrc/refit_levels_host.h", "csrc/rt_rng.h",
+                 "csrc/rng_table_host.h", "../include/rtamd.h")
 
 
 def source_hash() -> str:
@@ -282,6 +284,9 @@ def lib() -> C.CDLL:
                 "rt_refit_scene": (i32, [dp, sz, C.POINTER(C.c_uint32), sz, fp, vp, sz]),
                 "rt_accel_refit_records": (i32, [C.POINTER(C.c_uint32), sz, i32, vp, sz, vp, sz]),
                 "rt_scene_copy_records": (i32, [vp, i32, C.POINTER(C.c_uint32), sz, C.POINTER(sz)]),
+                "rt_rng_table_bytes": (i32, [i32, i32, i32, C.POINTER(C.c_uint64)]),
+                "rt_rng_table_copy": (i32, [vp, vp, sz, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+                "rt_rng_table_launch_key": (i32, [vp, i32, C.POINTER(C.c_uint64), sz, C.POINTER(sz)]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)

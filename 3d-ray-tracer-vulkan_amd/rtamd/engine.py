@@ -556,6 +556,19 @@ class Renderer:
         out.update(order=order, mask=mask, hpix=hpix, records=rec, lanes=lanes)
         return out
 
+    # --- option rng_table's table (include/rtamd.h rt_rng_table_copy) ---
+    def rng_table_copy(self):
+        """Device 0's table of scatter draws as (words, width, height, k): words
+        is uint32 [k, height, width, 4], a float's bits in .x .y .z and the seed
+        in .w; (None, 0, 0, 0) when the device holds none.  Not for timing runs."""
+        w, h, k = C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().rt_rng_table_copy(self._ctx, None, 0, C.byref(w), C.byref(h), C.byref(k)))
+        if k.value == 0:
+            return None, 0, 0, 0
+        words = np.empty((k.value, h.value, w.value, 4), np.uint32)
+        check(lib().rt_rng_table_copy(self._ctx, words.ctypes.data, words.nbytes, None, None, None))
+        return words, w.value, h.value, k.value
+
 
 class PinnedFrame:
     """An RGBA8 frame in pinned host memory (rt_host_alloc), as a numpy view."""

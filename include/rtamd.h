@@ -854,6 +854,31 @@ int rt_render_samples(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int heig
  *   "split_overflow" (rt_get_option only; diagnostic, waits for the devices)
  *                   kernel-1 waves whose claim did not fit their queue since
  *                   the last read
+ *   "rng_table"     K in 0..64: the first K bounces of a path read their
+ *                   scatter draw (the shader's randomVec3InUnitSphere point
+ *                   and the seed after it) from a table instead of computing
+ *                   it.  A path's draws depend on its pixel and the bounce
+ *                   alone, not on the scene or the camera, so the table is
+ *                   built once per device and frame size (width x height x K
+ *                   entries of 16 B: 66 MB for 1920x1080 at K = 2) by the
+ *                   first launch that needs it, which waits for it on the
+ *                   host; another frame size or K replaces it, after waiting
+ *                   for the device.  Same frames, bit for bit.  Format-0
+ *                   accel records without a cooperative tail only; learning
+ *                   and extension launches ("new_sample", samples,
+ *                   accumulation) compute their draws.  0 = no table: the
+ *                   kernels without it.  Default 2
+ *   "rng_table_pixels" only a launch of at least this many pixels (all its
+ *                   frames together) reads the table: launches of 4 frames of
+ *                   1920x1080 measured 3.2% faster with it, launches of one such
+ *                   frame 8% slower (a small launch is bound by its waves'
+ *                   latency, to which the table's load adds).
+ *                   0..2^30, default 8000000
+ *   "rng_table_mb"  the most memory (MiB) a device's table may take: a launch
+ *                   whose table would be larger, or does not fit the device,
+ *                   computes its draws.  0..2^20, default 512
+ *   "rng_table_used" (rt_get_option only) the K device 0's last launch read
+ *                   from the table, 0 when it computed its draws
  *   "accel_half"    at the next rt_upload_scene, accel records with the
  *                   internal nodes' boxes in IEEE half precision rounded
  *                   outward (16-B internal records instead of 32; leaves keep
@@ -1205,6 +1230,22 @@ typedef struct rt_learn_info {
  * RT_ERR_INVALID_ARG when nothing has been learned.  Not for timing runs. */
 int rt_learn_copy(rt_ctx* ctx, rt_learn_info* info, int32_t* order, uint64_t* mask, int32_t* hpix,
                   uint64_t* records, uint32_t* lanes);
+
+/* Option "rng_table"'s table, for tests and tools.
+ * rt_rng_table_bytes: *bytes = the table's size for a width x height frame
+ * and K = k bounces, 0 where there is none (a side or k below 1, k above 64,
+ * more than 2^27 pixels); needs no device.
+ * rt_rng_table_copy: waits for device 0 and copies its table to dst (nullable;
+ * at most cap_bytes), planes by bounce: entry k * width * height + y * width + x
+ * is 4 32-bit words, the point's x, y, z as floats and the seed after the
+ * draw.  *width, *height, *k (nullable) = what the table was built for, all 0
+ * when the device holds none.
+ * rt_rng_table_launch_key: the key a launch is compared by (option "graph")
+ * for a launch that differs from a default one in its table pointer and K
+ * alone: *n words (at most cap are written to key); needs no device. */
+int rt_rng_table_bytes(int width, int height, int k, uint64_t* bytes);
+int rt_rng_table_copy(rt_ctx* ctx, void* dst, size_t cap_bytes, int* width, int* height, int* k);
+int rt_rng_table_launch_key(const void* table, int k, uint64_t* key, size_t cap, size_t* n);
 
 /* Replaces VulkanEngine.cleanup. Null is accepted. */
 int rt_destroy(rt_ctx* ctx);
