@@ -131,8 +131,9 @@ constexpr int kWideStack = 12;
 float wide_decode(float origin, int q, int e);
 
 // Builds the records from the reference's buffers (the rt_upload_scene
-// inputs: 48-B vertex records, 16-B materials, 48-B preorder nodes).  The
-// buffers must already have passed build_host_scene's validation, and
+// inputs: 48-B vertex records, 16-B materials, 48-B preorder nodes; plan_scene
+// of scene_plan.cpp calls it for an upload).  The buffers must already have
+// passed build_host_scene's validation (scene_plan.h), and
 // bvh_bytes must cover only the nodes the root's subtree holds (HostScene::end
 // x 48): a node past the root's skip is never visited by the reference's DFS
 // (compute_dynamic_ray.comp:185-210), so its leaf is not a primitive.  Returns

@@ -1,7 +1,8 @@
 // rt_internal.h — shared declarations of the gfx950 path-trace backend.
 //
-// Device layout of a scene (built once per rt_upload_scene from the
-// reference's 48-B node / 48-B vertex / 16-B material records):
+// Device layout of a scene (laid out on the host once per rt_upload_scene, by
+// plan_scene of scene_plan.cpp, from the reference's 48-B node / 48-B vertex /
+// 16-B material records):
 //
 //   nodes : 2 x float4 per node (32 B), in the reference's preorder
 //           [0] = (bbox_min.xyz, skip | L(skip) << 31)
@@ -38,10 +39,9 @@
 
 #include "../../include/rtamd.h"
 #include "rng_table_host.h"
+#include "scene_plan.h"      // kShadeStride, kRefitStatusWords
 
 namespace rtamd {
-
-constexpr int kShadeStride = 2;
 
 struct DevScene {
     int      n_nodes = 0;     // nodes in the compact array
@@ -229,23 +229,6 @@ struct TraceArgs {
     int      rng_k = 0;
 };
 
-// Host-side compact-scene build from the reference records; validates the
-// buffers.  Returns RT_OK or RT_ERR_BAD_SCENE with a message in *err.
-struct HostScene {
-    int n_nodes = 0, end = 0, n_tris = 0, max_depth = 0, root_leaf = 0;
-    float root_box[6] = {0, 0, 0, 0, 0, 0};
-    float4* nodes = nullptr;    // 2*n_nodes
-    float4* leafs = nullptr;    // 3*n_nodes
-    float4* pairs = nullptr;    // 4*n_nodes
-    float4* norms = nullptr;    // n_tris
-    float4* mats  = nullptr;    // n_tris
-};
-int build_host_scene(const void* vertices, size_t vertex_bytes,
-                     const void* materials, size_t material_bytes,
-                     const void* bvh_nodes, size_t bvh_bytes,
-                     HostScene* out, const char** err);
-void free_host_scene(HostScene* s);
-
 // A learning launch's walk length of a pixel traced by a one-pixel heavy wave
 // (its lockstep length is unknown there): above any real length, so it stays
 // among the heavy pixels (rt_learn.hip).
@@ -398,6 +381,7 @@ hipError_t launch_samples_resolve(const SamplesArgs& r, hipStream_t stream);
 struct RefitTables {
     const float4* st_verts = nullptr;   // staging: the raw vertex records, 3 float4 per flattened triangle
     const float*  st_boxes = nullptr;   // staging: 6 floats per reference node (min.xyz, max.xyz)
+    // the tables: sections of one byte blob laid out by scene_plan.cpp (RefitLayout names their offsets)
     int           n_ref = 0;            // reference nodes of the root's subtree (HostScene::end)
     int           n_tris = 0;           // flattened triangles
     const int*    ref_info = nullptr;   // per reference node: a leaf's triangle, or -(right child + 1)
@@ -434,8 +418,8 @@ struct RefitFront {
     int             n_dups = 0;
     unsigned*       status = nullptr;    // kRefitStatusWords words: the lowest offending flattened triangle per kind
 };
-constexpr int kRefitStatusWords = 4;     // [0] a source entry >= n_in, [1] a cast that is not finite,
-                                         // [2] a dropped duplicate that no longer is one, [3] unused
+// kRefitStatusWords (scene_plan.h) words: [0] a source entry >= n_in, [1] a cast that is not finite,
+// [2] a dropped duplicate that no longer is one, [3] unused
 // The check: reads the input only, and sets status (every word 0xFFFFFFFF where nothing offends).
 hipError_t launch_refit_check(const RefitFront& f, hipStream_t stream);
 // The stage kernel, the leaf boxes and one launch per level; level_first: n_levels + 1 offsets into by_height.

@@ -5,8 +5,8 @@
 // node boxes (24 B per node); everything else is computed here, with the
 // host's operations in the host's order.  The library is built with
 // -ffp-contract=off and `/`, sqrtf and the double sqrt and division are
-// correctly rounded, so the bits are the ones build_host_scene, the walk-record
-// loop of rt_upload_scene and accel_build write for the same buffers.
+// correctly rounded, so the bits are the ones build_host_scene and the
+// walk-record loop of scene_plan.cpp and accel_build write for the same buffers.
 //
 // Three stages on one stream, each a plain grid of independent lanes:
 //   refit_reference : a lane per reference node (and per flattened triangle,

@@ -4,7 +4,7 @@
 // barriers, staging image) has no counterpart: device buffers + one HIP
 // stream per device.
 #include "rt_internal.h"
-#include "refit_levels_host.h"
+#include "scene_plan.h"
 #include "temporal_motion_host.h"
 
 #include "accel_build.h"
@@ -40,8 +40,6 @@ void set_error(const char* fmt, ...) {
         }                                                                         \
     } while (0)
 
-// ------------------------------------------------------------ scene build --
-
 // The accel records' slot cap: 0 = the hardware's (accel_build.h).  Tests
 // lower it through RTAMD_ACCEL_CAP_SLOTS to drive the capacity fallback.
 static int64_t accel_cap_slots() {
@@ -53,168 +51,6 @@ static inline float f32_at(const unsigned char* p, size_t off) {
     float f;
     std::memcpy(&f, p + off, 4);
     return f;
-}
-static inline int32_t i32_at(const unsigned char* p, size_t off) {
-    int32_t v;
-    std::memcpy(&v, p + off, 4);
-    return v;
-}
-
-void free_host_scene(HostScene* s) {
-    std::free(s->nodes);
-    std::free(s->leafs);
-    std::free(s->pairs);
-    std::free(s->norms);
-    std::free(s->mats);
-    *s = HostScene{};
-}
-
-int build_host_scene(const void* vertices, size_t vertex_bytes,
-                     const void* materials, size_t material_bytes,
-                     const void* bvh_nodes, size_t bvh_bytes,
-                     HostScene* out, const char** err) {
-    static thread_local std::string msg;
-    *out = HostScene{};
-    const size_t n_nodes = bvh_bytes < RT_NODE_RECORD_BYTES ? 0 : bvh_bytes / RT_NODE_RECORD_BYTES;
-    const size_t n_tris  = vertex_bytes < RT_VERTEX_RECORD_BYTES ? 0 : vertex_bytes / RT_VERTEX_RECORD_BYTES;
-    const size_t n_mats  = material_bytes < RT_MATERIAL_RECORD_BYTES ? 0 : material_bytes / RT_MATERIAL_RECORD_BYTES;
-    auto fail = [&](const std::string& m) {
-        msg = m;
-        *err = msg.c_str();
-        free_host_scene(out);
-        return RT_ERR_BAD_SCENE;
-    };
-    if (n_nodes && bvh_bytes % RT_NODE_RECORD_BYTES)
-        return fail("bvh_bytes is not a multiple of 48");
-    if (n_tris && vertex_bytes % RT_VERTEX_RECORD_BYTES)
-        return fail("vertex_bytes is not a multiple of 48");
-    if (n_mats && material_bytes % RT_MATERIAL_RECORD_BYTES)
-        return fail("material_bytes is not a multiple of 16");
-    if (n_nodes > (size_t)INT32_MAX / 2 || n_tris > (size_t)INT32_MAX / 3)
-        return fail("scene too large for 32-bit node/triangle indices");
-    if (n_nodes && (!bvh_nodes)) return fail("null bvh buffer");
-    if (n_tris && (!vertices)) return fail("null vertex buffer");
-    if (n_mats && (!materials)) return fail("null material buffer");
-
-    out->n_nodes = (int)n_nodes;
-    out->n_tris  = (int)n_tris;
-    if (n_nodes == 0) {
-        out->end = 0;   // empty scene: every ray misses (reference: undefined read of node 0)
-        return RT_OK;
-    }
-    const unsigned char* nb = static_cast<const unsigned char*>(bvh_nodes);
-    std::vector<int32_t> skip(n_nodes), depth(n_nodes, 0);
-    out->nodes = static_cast<float4*>(std::malloc(sizeof(float4) * 2 * n_nodes));
-    if (!out->nodes) return fail("out of host memory");
-
-    // Pass 1 (reverse): leaf skip = i+1, internal skip = skip(right).  The
-    // layout must be the reference flattener's preorder: left == i+1 and the
-    // left subtree ends exactly where the right child starts.
-    for (size_t k = n_nodes; k-- > 0;) {
-        const unsigned char* r = nb + k * RT_NODE_RECORD_BYTES;
-        const int32_t data = i32_at(r, 32), count = i32_at(r, 36);
-        if (count < 0) {                                   // leaf (compute_dynamic_ray.comp:194-195)
-            const int64_t tri = -((int64_t)data + 1);
-            if (tri < 0 || (size_t)tri >= n_tris || (size_t)tri >= n_mats)
-                return fail("leaf node " + std::to_string(k) + " references triangle " +
-                            std::to_string(tri) + " outside the vertex/material buffers");
-            skip[k] = (int32_t)(k + 1);
-        } else {
-            if ((size_t)data != k + 1 || count <= data || (size_t)count >= n_nodes)
-                return fail("node " + std::to_string(k) +
-                            " is not in the reference's preorder layout (left must be i+1, right > left)");
-            if (skip[data] != count)
-                return fail("node " + std::to_string(k) + ": left subtree does not end at the right child");
-            skip[k] = skip[count];
-        }
-    }
-    out->end = skip[0];
-    std::vector<uint8_t> is_leaf(n_nodes + 1, 0);
-    for (size_t k = 0; k < n_nodes; ++k) is_leaf[k] = i32_at(nb + k * RT_NODE_RECORD_BYTES, 36) < 0;
-    out->root_leaf = is_leaf[0];
-    out->leafs = static_cast<float4*>(std::calloc(3 * n_nodes, sizeof(float4)));
-    out->pairs = static_cast<float4*>(std::calloc(4 * n_nodes, sizeof(float4)));
-    if (!out->leafs || !out->pairs) return fail("out of host memory");
-    const unsigned char* vb = static_cast<const unsigned char*>(vertices);
-    int max_depth = 0;
-    for (size_t k = 0; k < (size_t)out->end; ++k) {
-        const unsigned char* r = nb + k * RT_NODE_RECORD_BYTES;
-        const int32_t data = i32_at(r, 32), count = i32_at(r, 36);
-        if (count >= 0) {
-            depth[data] = depth[k] + 1;
-            depth[count] = depth[k] + 1;
-        }
-        if (depth[k] > max_depth) max_depth = depth[k];
-        float4 A, B;
-        A.x = f32_at(r, 0);  A.y = f32_at(r, 4);  A.z = f32_at(r, 8);
-        B.x = f32_at(r, 16); B.y = f32_at(r, 20); B.z = f32_at(r, 24);
-        const uint32_t sk = (uint32_t)skip[k];
-        const uint32_t aw = sk | ((sk < (uint32_t)out->end && is_leaf[sk]) ? 0x80000000u : 0u);
-        const uint32_t bw = ((k + 1 < (size_t)out->end && is_leaf[k + 1]) ? 1u : 0u) | (is_leaf[k] ? 2u : 0u);
-        std::memcpy(&A.w, &aw, 4);
-        std::memcpy(&B.w, &bw, 4);
-        out->nodes[2 * k] = A;
-        out->nodes[2 * k + 1] = B;
-        if (k == 0) {
-            out->root_box[0] = A.x; out->root_box[1] = A.y; out->root_box[2] = A.z;
-            out->root_box[3] = B.x; out->root_box[4] = B.y; out->root_box[5] = B.z;
-        }
-        if (count >= 0) {
-            const unsigned char* l = nb + (size_t)data * RT_NODE_RECORD_BYTES;
-            const unsigned char* rr = nb + (size_t)count * RT_NODE_RECORD_BYTES;
-            const uint32_t rw = (uint32_t)count | (is_leaf[count] ? 0x80000000u : 0u);
-            const uint32_t lw = is_leaf[data] ? 1u : 0u;
-            const uint32_t sw = (uint32_t)skip[k];
-            float rwf, lwf, swf;
-            std::memcpy(&rwf, &rw, 4);
-            std::memcpy(&lwf, &lw, 4);
-            std::memcpy(&swf, &sw, 4);
-            out->pairs[4 * k + 0] = make_float4(f32_at(l, 0), f32_at(l, 4), f32_at(l, 8), f32_at(rr, 0));
-            out->pairs[4 * k + 1] = make_float4(f32_at(l, 16), f32_at(l, 20), f32_at(l, 24), f32_at(rr, 4));
-            out->pairs[4 * k + 2] = make_float4(f32_at(rr, 16), f32_at(rr, 20), f32_at(rr, 24), f32_at(rr, 8));
-            out->pairs[4 * k + 3] = make_float4(rwf, lwf, swf, 0.f);
-        }
-        if (count < 0) {
-            // edge1 / edge2 exactly as hit_triangle computes them (compute_dynamic_ray.comp:106-107)
-            const int32_t tri = -(data + 1);
-            const unsigned char* v = vb + (size_t)tri * RT_VERTEX_RECORD_BYTES;
-            const float v0x = f32_at(v, 0),  v0y = f32_at(v, 4),  v0z = f32_at(v, 8);
-            const float v1x = f32_at(v, 16), v1y = f32_at(v, 20), v1z = f32_at(v, 24);
-            const float v2x = f32_at(v, 32), v2y = f32_at(v, 36), v2z = f32_at(v, 40);
-            float tw;
-            std::memcpy(&tw, &tri, 4);
-            out->leafs[3 * k + 0] = make_float4(v0x, v0y, v0z, tw);
-            out->leafs[3 * k + 1] = make_float4(v1x - v0x, v1y - v0y, v1z - v0z, 0.f);
-            out->leafs[3 * k + 2] = make_float4(v2x - v0x, v2y - v0y, v2z - v0z, 0.f);
-        }
-    }
-    out->max_depth = max_depth;
-
-    out->norms = static_cast<float4*>(std::malloc(sizeof(float4) * (n_tris ? n_tris : 1)));
-    out->mats = static_cast<float4*>(std::malloc(sizeof(float4) * (n_tris ? n_tris : 1)));
-    if (!out->norms || !out->mats) return fail("out of host memory");
-    const unsigned char* mb = static_cast<const unsigned char*>(materials);
-    for (size_t t = 0; t < n_tris; ++t) {
-        const unsigned char* r = vb + t * RT_VERTEX_RECORD_BYTES;
-        const float v0x = f32_at(r, 0),  v0y = f32_at(r, 4),  v0z = f32_at(r, 8);
-        const float v1x = f32_at(r, 16), v1y = f32_at(r, 20), v1z = f32_at(r, 24);
-        const float v2x = f32_at(r, 32), v2y = f32_at(r, 36), v2z = f32_at(r, 40);
-        // normalize(cross(edge1, edge2)) exactly as hit_triangle computes it (:124)
-        const float e1x = v1x - v0x, e1y = v1y - v0y, e1z = v1z - v0z;
-        const float e2x = v2x - v0x, e2y = v2y - v0y, e2z = v2z - v0z;
-        const float cx = e1y * e2z - e1z * e2y;
-        const float cy = e1z * e2x - e1x * e2z;
-        const float cz = e1x * e2y - e1y * e2x;
-        const float l = std::sqrt((cx * cx + cy * cy) + cz * cz);
-        out->norms[t] = make_float4(cx / l, cy / l, cz / l, 0.f);
-        if (t < n_mats) {
-            const unsigned char* m = mb + t * RT_MATERIAL_RECORD_BYTES;
-            out->mats[t] = make_float4(f32_at(m, 0), f32_at(m, 4), f32_at(m, 8), f32_at(m, 12));
-        } else {
-            out->mats[t] = make_float4(0.f, 0.f, 0.f, -1.f);   // never referenced (validated above)
-        }
-    }
-    return RT_OK;
 }
 
 }  // namespace rtamd
@@ -373,11 +209,6 @@ struct PerDevice {
 static constexpr size_t kMaxOrders = 16;
 static constexpr int    kResidentPerCu = 24;    // resident trace waves per CU (diag timelines)
 static constexpr int    kMaxHeavy = 256;
-// coop_window 0: scenes whose walk records exceed the 8 XCDs' L2s together
-// (8 x 4 MB) take 32-slot windows: config 5 (100 MB) fetched 22.4 instead of
-// 28.5 GB per frame at the same frame time; config 3 (6.3 MB, L2-resident)
-// is 1.2% faster with 64 (profiles/r04/r4f).
-static constexpr size_t kWin32Bytes = 32ull << 20;
 // split launches: the largest queue allocation per launch stream
 static constexpr size_t kSplitSlotBytes = 256ull << 20;
 // option split_pixels' default: launches of 3 or more 1920x1080 frames, or of
@@ -393,9 +224,6 @@ static constexpr int kRngTableMbDefault = 512;
 // option rng_table_pixels' default: launches of 4 frames of 1920x1080 measured 3.2% faster with the table
 // (config 3; one 3840x2160 frame: even), launches of 1 frame 8% slower (profiles/rng_table)
 static constexpr int kRngTablePixelsDefault = 8000000;
-// The walk's buffer loads address the records with 32-bit byte offsets
-// (rt_trace.hip wbuf): at most 2^27 - 4 slots of 32 B (~45M triangles).
-static constexpr unsigned kMaxWalkSlots = (1u << 27) - 4;
 static constexpr size_t kDiagWords = 8;   // per-wave diag record (rt_trace.hip, rtamd.h rt_diag_copy)
 
 static void free_order(PerDevice::Order& o) {
@@ -1495,196 +1323,22 @@ int rt_destroy(rt_ctx* ctx) {
     return RT_OK;
 }
 
+// The layout is plan_scene's (scene_plan.h): every array arrives as the bytes
+// the device gets, and this function allocates, copies and points into them.
 int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
                     const void* materials, size_t material_bytes,
                     const void* bvh_nodes, size_t bvh_bytes) {
     if (!ctx) { set_error("rt_upload_scene: null context"); return RT_ERR_INVALID_ARG; }
-    HostScene hs;
-    const char* err = nullptr;
-    int rc = build_host_scene(vertices, vertex_bytes, materials, material_bytes,
-                              bvh_nodes, bvh_bytes, &hs, &err);
-    if (rc != RT_OK) { set_error("rt_upload_scene: %s", err); return rc; }
-    // walk 2's records (DevScene::walk; rt_internal.h): the reference's
-    // preorder with every leaf's triangle inlined after its box, so an
-    // internal node takes one 32-B slot and a leaf two.  slot(i) = i + the
-    // leaves before i; an internal node's left child is the next slot, a
-    // leaf's successor (its skip, i+1) the slot after its two, and only the
-    // internal skip is stored, as a slot.  The visit sequence is the
-    // reference's, node for node.
-    // Option leaf_align: a leaf that would start in the last slot of a 128-B
-    // line (and straddle two) starts one slot later; its predecessor's pad bit
-    // (a leaf's bit 29 of word [0].w, an internal node's bit 2 of word [1].w)
-    // tells the walk to step over the pad slot.
-    // Only the root's subtree, [0, end): nodes past the root's skip are
-    // never visited by the reference's DFS (compute_dynamic_ray.comp:185-210).
-    const size_t n2 = (size_t)hs.end;
-    std::vector<int> slot(n2 + 1);
-    std::vector<uint8_t> padded(n2 + 1, 0);       // a pad slot precedes node i
-    size_t n_leaves = 0;
-    for (size_t i = 0; i < n2; ++i) {
-        uint32_t fl;
-        std::memcpy(&fl, &hs.nodes[2 * i + 1].w, 4);
-        n_leaves += (fl & 2u) ? 1 : 0;
-    }
-    const bool align = ctx->leaf_align == 1 || (ctx->leaf_align == 2 && (n2 + n_leaves) * 32 > kWin32Bytes);
-    size_t nslot = 0, n_pads = 0;
-    for (size_t i = 0; i < n2; ++i) {
-        uint32_t fl;
-        std::memcpy(&fl, &hs.nodes[2 * i + 1].w, 4);
-        if (align && (fl & 2u) && nslot % 4 == 3) {
-            padded[i] = 1;
-            ++nslot;
-            ++n_pads;
-        }
-        slot[i] = (int)nslot;
-        nslot += (fl & 2u) ? 2 : 1;
-        if (nslot >= kMaxWalkSlots) {
-            free_host_scene(&hs);
-            set_error("rt_upload_scene: %zu nodes: at most %u walk slots (4 GB of walk records) supported", n2,
-                      kMaxWalkSlots);
-            return RT_ERR_BAD_SCENE;
-        }
-    }
-    slot[n2] = (int)nslot;
-    std::vector<float4> walk(2 * nslot + 4, make_float4(0.f, 0.f, 0.f, 0.f));   // + padding read at the end
-    std::vector<int> slot_node(nslot + 1, -1);
-    for (size_t i = 0; i < n2; ++i) {
-        const size_t w = 2 * (size_t)slot[i];
-        slot_node[slot[i]] = (int)i;
-        walk[w] = hs.nodes[2 * i];
-        walk[w + 1] = hs.nodes[2 * i + 1];
-        uint32_t fl, link;
-        std::memcpy(&fl, &hs.nodes[2 * i + 1].w, 4);
-        std::memcpy(&link, &hs.nodes[2 * i].w, 4);
-        if (!(fl & 2u)) {                                   // internal: the skip as a slot (< 2^30: bit 30 clear)
-            const uint32_t sk = link & 0x7FFFFFFFu;
-            const uint32_t w0 = (uint32_t)slot[sk] | (link & 0x80000000u);
-            std::memcpy(&walk[w].w, &w0, 4);
-            if (padded[i + 1]) {                            // the left child (i+1) sits past a pad slot
-                uint32_t w1;
-                std::memcpy(&w1, &walk[w + 1].w, 4);
-                w1 |= 4u;
-                std::memcpy(&walk[w + 1].w, &w1, 4);
-            }
-            continue;
-        }
-        uint32_t tri;
-        std::memcpy(&tri, &hs.leafs[3 * i].w, 4);
-        if ((link & 0x7FFFFFFFu) != i + 1 || tri >= (1u << 29)) {
-            free_host_scene(&hs);
-            set_error("rt_upload_scene: leaf %zu: skip %u is not i+1 or triangle index %u too large", i,
-                      link & 0x7FFFFFFFu, tri);
-            return RT_ERR_BAD_SCENE;
-        }
-        const uint32_t w0 = tri | (padded[i + 1] ? 1u << 29 : 0u) | (1u << 30) | (link & 0x80000000u);
-        std::memcpy(&walk[w].w, &w0, 4);
-        walk[w + 1].w = hs.leafs[3 * i].x;                                   // v0.x
-        const float4 P0 = hs.leafs[3 * i], P1 = hs.leafs[3 * i + 1], P2 = hs.leafs[3 * i + 2];
-        walk[w + 2] = make_float4(P0.y, P0.z, P1.x, P1.y);                   // v0.yz, e1.xy
-        walk[w + 3] = make_float4(P1.z, P2.x, P2.y, P2.z);                   // e1.z, e2
-    }
-    // Option accel: the binned-SAH records (accel_build.h), built once for
-    // every device; the reference's walk records above stay beside them for
-    // the fallback, and the node-indexed arrays (walk 0, the frontier walk of
-    // heavy pixels) are not needed.
-    // Past the slot cap 8 layouts become 1, and a scene too large for one
-    // walks the reference's own tree (accel_used says which: 8, 1 or 0).
-    AccelHost ah;
-    bool acc = false;
-    if (ctx->accel) {
-        std::string msg;
-        const int rc = accel_build_fit(vertices, vertex_bytes, materials, material_bytes, bvh_nodes,
-                                       (size_t)hs.end * RT_NODE_RECORD_BYTES, ctx->accel, &ah, &msg,
-                                       ctx->accel_wide ? 2 : ctx->accel_half ? 1 : 0, accel_cap_slots(),
-                                       ctx->refit != 0);
-        if (rc != 0 && rc != kAccelTooBig) {
-            free_host_scene(&hs);
-            set_error("rt_upload_scene: %s", msg.c_str());
-            return RT_ERR_BAD_SCENE;
-        }
-        acc = rc == 0;
-    }
-    // Option refit: what rt_update_geometry needs, laid out once as the bytes every device
-    // gets behind its staging buffers.  The half and wide record formats hold none.
+    const PlanOptions opt = {ctx->leaf_align, ctx->accel,        ctx->accel_half,  ctx->accel_wide,
+                             ctx->refit,      ctx->refit_device, accel_cap_slots()};
+    ScenePlan plan;
+    std::string err;
+    const int rc = plan_scene(vertices, vertex_bytes, materials, material_bytes, bvh_nodes, bvh_bytes, opt, &plan, &err);
+    if (rc != RT_OK) { set_error("rt_upload_scene: %s", err.c_str()); return rc; }
+    const HostScene& hs = plan.host;
+    const RefitLayout& rl = plan.rl;
     ctx->refit_held = false;
     ctx->refit_device_held = false;
-    bool front = false;
-    size_t o_fheight = 0, o_fdups = 0, o_fstatus = 0;
-    const bool keep = ctx->refit && !(acc && ah.format != 0);
-    std::vector<uint8_t> rtab;                 // the tables, sections 16-B aligned
-    size_t o_info = 0, o_slot = 0, o_prim = 0, o_child = 0, o_lslot = 0, o_height = 0, o_canon = 0;
-    const size_t st_bytes = ((size_t)hs.n_tris * 48 + (size_t)hs.n_nodes * 24 + 15) / 16 * 16;
-    if (keep) {
-        const auto section = [&rtab](size_t bytes) {
-            const size_t at = rtab.size();
-            rtab.resize(at + (bytes + 15) / 16 * 16, 0);
-            return at;
-        };
-        o_info = section(4 * n2);
-        o_slot = section(4 * n2);
-        for (size_t i = 0; i < n2; ++i) {
-            uint32_t fl, v;
-            std::memcpy(&fl, &hs.nodes[2 * i + 1].w, 4);
-            if (fl & 2u) std::memcpy(&v, &hs.leafs[3 * i].w, 4);                 // the triangle
-            else {
-                std::memcpy(&v, &hs.pairs[4 * i + 3].x, 4);                      // the right child
-                v = (uint32_t)(-(int32_t)((v & 0x7FFFFFFFu) + 1));
-            }
-            std::memcpy(&rtab[o_info + 4 * i], &v, 4);
-            std::memcpy(&rtab[o_slot + 4 * i], &slot[i], 4);
-        }
-        ctx->refit_level_first.assign(1, 0);
-        if (acc && ah.slots > 0) {
-            const size_t m = ah.prim_tri.size(), nc = ah.node_height.size();
-            o_prim = section(12 * m);
-            for (size_t k = 0; k < m; ++k) {
-                const int32_t rec[3] = {ah.prim_tri[k], ah.prim_leaf[k], ah.prim_node[k]};
-                std::memcpy(&rtab[o_prim + 12 * k], rec, 12);
-            }
-            o_child = section(8 * nc);
-            std::memcpy(&rtab[o_child], ah.node_child.data(), 8 * nc);
-            o_lslot = section(4 * nc * (size_t)ah.n_layouts);
-            std::memcpy(&rtab[o_lslot], ah.node_slot.data(), 4 * nc * (size_t)ah.n_layouts);
-            // the internal nodes by height, lowest first (a counting sort), and where each height starts
-            int top = 0;
-            for (size_t c = 0; c < nc; ++c) top = std::max(top, ah.node_height[c]);
-            std::vector<int> first(top + 2, 0);
-            for (size_t c = 0; c < nc; ++c)
-                if (ah.node_height[c] > 0) ++first[ah.node_height[c] + 1];
-            for (int h = 1; h <= top + 1; ++h) first[h] += first[h - 1];
-            o_height = section(4 * (nc - m));
-            std::vector<int> at(first.begin(), first.end());
-            for (size_t c = 0; c < nc; ++c)
-                if (ah.node_height[c] > 0) {
-                    const int32_t id = (int32_t)c;
-                    std::memcpy(&rtab[o_height + 4 * (size_t)at[ah.node_height[c]]++], &id, 4);
-                }
-            ctx->refit_level_first.assign(first.begin() + 1, first.end());       // heights 1 .. top, then the end
-            o_canon = section(32 * nc);
-        }
-        const unsigned char* nbytes = static_cast<const unsigned char*>(bvh_nodes);
-        ctx->refit_links.resize(24 * (size_t)hs.n_nodes);
-        for (size_t i = 0; i < (size_t)hs.n_nodes; ++i) {
-            std::memcpy(&ctx->refit_links[24 * i], nbytes + 48 * i + 12, 4);
-            std::memcpy(&ctx->refit_links[24 * i + 4], nbytes + 48 * i + 28, 20);
-        }
-        ctx->refit_dups = acc ? ah.dup_pairs : std::vector<int32_t>();
-        ctx->refit_vertex_bytes = vertex_bytes;
-        ctx->refit_bvh_bytes = bvh_bytes;
-        // Option refit_device: the reference nodes by height, the dropped duplicates and
-        // the check's status words behind the tables above, which stay where they are without it
-        std::vector<int32_t> by_height;
-        front = ctx->refit_device != 0 &&
-                refit_levels(reinterpret_cast<const int32_t*>(rtab.data() + o_info), n2, &by_height, &ctx->refit_front_first);
-        if (front) {
-            o_fheight = section(4 * n2);
-            if (n2) std::memcpy(&rtab[o_fheight], by_height.data(), 4 * n2);
-            o_fdups = section(4 * ctx->refit_dups.size());
-            if (!ctx->refit_dups.empty())
-                std::memcpy(&rtab[o_fdups], ctx->refit_dups.data(), 4 * ctx->refit_dups.size());
-            o_fstatus = section(sizeof(unsigned) * kRefitStatusWords);
-        }
-    }
     ctx->has_scene = false;
     for (PerDevice& p : ctx->dev) {
         RT_HIP_CHECK(hipSetDevice(p.device));
@@ -1701,129 +1355,111 @@ int rt_upload_scene(rt_ctx* ctx, const void* vertices, size_t vertex_bytes,
         s.n_tris = hs.n_tris;
         s.root_leaf = hs.root_leaf;
         std::memcpy(s.root_box, hs.root_box, sizeof s.root_box);
-        // nodes and leafs are padded by one record: walks read the record at
-        // index end (the node after the last) before they test for the end.
-        const size_t nn = (size_t)hs.n_nodes;
-        const size_t nb = sizeof(float4) * (2 * nn + 2);
-        const size_t lb = sizeof(float4) * (3 * nn + 1);
-        const size_t pb = sizeof(float4) * 4 * (size_t)(hs.n_nodes ? hs.n_nodes : 1);
-        const size_t mb = sizeof(float4) * (size_t)(hs.n_tris ? hs.n_tris : 1);
-        hipError_t e = hipSuccess;
-        if (acc) {
-            s.n_layouts = ah.n_layouts;
-            s.layout_slots = ah.slots;
-            s.half = ah.format == 1 ? 1 : 0;
-            s.wide = ah.format == 2 ? 1 : 0;
-            s.relax_half = ah.relax_max;
-            s.root_enter = ah.format == 0 && !ah.root_leaf && ah.slots > 1 ? 1 : 0;
-            s.root_first_leaf = 0;
-            if (s.root_enter)
-                for (int o = 0; o < ah.n_layouts; ++o)
-                    s.root_first_leaf |= (int)(ah.rec[8 * (size_t)o * (size_t)ah.slots + 7] >> 31) << o;
-            s.end = ah.slots;
-            s.end2 = ah.n_layouts * ah.slots;
-            s.root_leaf = ah.root_leaf;
-            s.end2_ref = (int)nslot;
-            s.ref_padded = n_pads > 0 ? 1 : 0;
-            e = hipMalloc(&s.walk, ah.rec.size() * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMalloc(&s.walk_ref, walk.size() * sizeof(float4));
-            if (e == hipSuccess)
-                e = hipMemcpy(s.walk, ah.rec.data(), ah.rec.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-            if (e == hipSuccess)
-                e = hipMemcpy(s.walk_ref, walk.data(), walk.size() * sizeof(float4), hipMemcpyHostToDevice);
+        if (plan.has_accel) {
+            s.n_layouts = plan.n_layouts;
+            s.layout_slots = plan.layout_slots;
+            s.half = plan.half;
+            s.wide = plan.wide;
+            s.relax_half = plan.relax_half;
+            s.root_enter = plan.root_enter;
+            s.root_first_leaf = plan.root_first_leaf;
+            s.end = plan.layout_slots;
+            s.end2 = plan.n_layouts * plan.layout_slots;
+            s.root_leaf = plan.accel_root_leaf;
+            s.end2_ref = plan.slots;
+            s.ref_padded = plan.padded ? 1 : 0;
         } else {
-            e = hipMalloc(&s.nodes, nb);
-            if (e == hipSuccess) e = hipMalloc(&s.leafs, lb);
-            if (e == hipSuccess) e = hipMalloc(&s.pairs, pb);
-            if (e == hipSuccess) e = hipMemset(s.nodes + 2 * nn, 0, 2 * sizeof(float4));
-            if (e == hipSuccess) e = hipMemset(s.leafs + 3 * nn, 0, sizeof(float4));
-            s.end2 = (int)nslot;
-            s.padded = n_pads > 0 ? 1 : 0;
-            if (e == hipSuccess) e = hipMalloc(&s.walk, walk.size() * sizeof(float4));
-            if (e == hipSuccess) e = hipMalloc(&s.slot_node, slot_node.size() * sizeof(int));
-            if (e == hipSuccess) e = hipMalloc(&s.node_slot, slot.size() * sizeof(int));
-            if (e == hipSuccess)
-                e = hipMemcpy(s.node_slot, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(s.walk, walk.data(), walk.size() * sizeof(float4), hipMemcpyHostToDevice);
-            if (e == hipSuccess)
-                e = hipMemcpy(s.slot_node, slot_node.data(), slot_node.size() * sizeof(int), hipMemcpyHostToDevice);
-            if (e == hipSuccess && hs.n_nodes)
-                e = hipMemcpy(s.nodes, hs.nodes, nb - 2 * sizeof(float4), hipMemcpyHostToDevice);
-            if (e == hipSuccess && hs.n_nodes)
-                e = hipMemcpy(s.leafs, hs.leafs, lb - sizeof(float4), hipMemcpyHostToDevice);
-            if (e == hipSuccess && hs.n_nodes) e = hipMemcpy(s.pairs, hs.pairs, pb, hipMemcpyHostToDevice);
+            s.end2 = plan.slots;
+            s.padded = plan.padded ? 1 : 0;
         }
-        if (e == hipSuccess) e = hipMalloc(&s.norms, kShadeStride * mb);
+        // each array: allocated whole, and filled from `src` behind its first `skip` bytes
+        struct Array { void* dst; size_t bytes; const void* src; size_t skip; };
+        const auto whole = [](auto** dst, const auto& v) { return Array{dst, v.size() * sizeof v[0], v.data(), 0}; };
+        std::vector<Array> arrays;
+        if (plan.has_accel) {
+            arrays = {whole(&s.walk, plan.accel_rec), whole(&s.walk_ref, plan.walk)};
+        } else {
+            arrays = {whole(&s.nodes, hs.nodes), whole(&s.leafs, hs.leafs), whole(&s.pairs, hs.pairs),
+                      whole(&s.walk, plan.walk), whole(&s.slot_node, plan.slot_node), whole(&s.node_slot, plan.node_slot)};
+        }
+        arrays.push_back(whole(&s.norms, hs.shade));
+        if (plan.keep) {
+            p.refit_bytes = rl.staging_bytes + plan.refit.size();
+            arrays.push_back({&p.d_refit, p.refit_bytes, plan.refit.data(), rl.staging_bytes});
+        }
+        hipError_t e = hipSuccess;
+        for (const Array& a : arrays) {
+            void** dst = static_cast<void**>(a.dst);
+            if (e == hipSuccess) e = hipMalloc(dst, a.bytes ? a.bytes : 16);
+            if (e == hipSuccess && a.bytes > a.skip)
+                e = hipMemcpy(static_cast<char*>(*dst) + a.skip, a.src, a.bytes - a.skip, hipMemcpyHostToDevice);
+        }
         if (e == hipSuccess) s.mats = s.norms + 1;
-        if (e == hipSuccess && hs.n_tris)
-            e = hipMemcpy2D(s.norms, kShadeStride * sizeof(float4), hs.norms, sizeof(float4), sizeof(float4),
-                            (size_t)hs.n_tris, hipMemcpyHostToDevice);
-        if (e == hipSuccess && hs.n_tris)
-            e = hipMemcpy2D(s.mats, kShadeStride * sizeof(float4), hs.mats, sizeof(float4), sizeof(float4),
-                            (size_t)hs.n_tris, hipMemcpyHostToDevice);
-        if (e == hipSuccess && keep) {
-            p.refit_bytes = st_bytes + rtab.size();
-            e = hipMalloc(&p.d_refit, p.refit_bytes ? p.refit_bytes : 16);
-            if (e == hipSuccess && !rtab.empty())
-                e = hipMemcpy(p.d_refit + st_bytes, rtab.data(), rtab.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && plan.keep) {
             // Option temporal_motion: the state before the first update is the uploaded records, copied from
             // the caller's buffer into the staging array an update would fill (no memory of its own).
-            if (e == hipSuccess && ctx->temporal_motion && ctx->dev.size() == 1 && hs.n_tris) {
-                e = hipMemcpy(p.d_refit, vertices, (size_t)hs.n_tris * 48, hipMemcpyHostToDevice);
+            if (ctx->temporal_motion && ctx->dev.size() == 1 && hs.n_tris) {
+                e = hipMemcpy(p.d_refit, vertices, rl.staging_boxes, hipMemcpyHostToDevice);
                 p.motion.on_upload(e == hipSuccess);
             }
             RefitTables& t = p.refit;
-            char* tb = p.d_refit + st_bytes;
+            char* tb = p.d_refit + rl.staging_bytes;
             t.st_verts = reinterpret_cast<const float4*>(p.d_refit);
-            t.st_boxes = reinterpret_cast<const float*>(p.d_refit + (size_t)hs.n_tris * 48);
+            t.st_boxes = reinterpret_cast<const float*>(p.d_refit + rl.staging_boxes);
             t.n_ref = hs.end;
             t.n_tris = hs.n_tris;
-            t.ref_info = reinterpret_cast<const int*>(tb + o_info);
-            t.ref_slot = reinterpret_cast<const int*>(tb + o_slot);
-            if (acc && ah.slots > 0) {
-                t.n_layouts = ah.n_layouts;
-                t.n_canon = (int)ah.node_height.size();
-                t.n_prims = (int)ah.prim_tri.size();
-                t.prim = reinterpret_cast<const int*>(tb + o_prim);
-                t.child = reinterpret_cast<const int*>(tb + o_child);
-                t.slot = reinterpret_cast<const uint32_t*>(tb + o_lslot);
-                t.by_height = reinterpret_cast<const int*>(tb + o_height);
-                t.canon = reinterpret_cast<float4*>(tb + o_canon);
+            t.ref_info = reinterpret_cast<const int*>(tb + rl.info);
+            t.ref_slot = reinterpret_cast<const int*>(tb + rl.slot);
+            if (rl.has_accel) {
+                t.n_layouts = rl.n_layouts;
+                t.n_canon = rl.n_canon;
+                t.n_prims = rl.n_prims;
+                t.prim = reinterpret_cast<const int*>(tb + rl.prim);
+                t.child = reinterpret_cast<const int*>(tb + rl.child);
+                t.slot = reinterpret_cast<const uint32_t*>(tb + rl.layout_slot);
+                t.by_height = reinterpret_cast<const int*>(tb + rl.by_height);
+                t.canon = reinterpret_cast<float4*>(tb + rl.canon);
             }
-            if (front) {
+            if (plan.front) {
                 RefitFront& f = p.front;
                 f.n_flat = hs.n_tris;
                 f.st_verts = const_cast<float4*>(t.st_verts);
                 f.st_boxes = const_cast<float*>(t.st_boxes);
                 f.ref_info = t.ref_info;
-                f.by_height = reinterpret_cast<const int*>(tb + o_fheight);
-                f.dups = reinterpret_cast<const int*>(tb + o_fdups);
-                f.n_dups = (int)(ctx->refit_dups.size() / 4);
-                f.status = reinterpret_cast<unsigned*>(tb + o_fstatus);
+                f.by_height = reinterpret_cast<const int*>(tb + rl.front_by_height);
+                f.dups = reinterpret_cast<const int*>(tb + rl.front_dups);
+                f.n_dups = (int)(plan.refit_dups.size() / 4);
+                f.status = reinterpret_cast<unsigned*>(tb + rl.front_status);
             }
         }
-        // the padding memsets ran on the null stream: complete before any
-        // launch stream (non-blocking) reads the scene
+        // the copies ran on the null stream: complete before any launch stream
+        // (non-blocking) reads the scene
         if (e == hipSuccess) e = hipDeviceSynchronize();
         p.scene = s;
         p.ref_root_leaf = hs.root_leaf;
         if (e != hipSuccess) {
             set_error("rt_upload_scene: device %d: %s", p.device, hipGetErrorString(e));
             free_scene(p);
-            free_host_scene(&hs);
             return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
         }
+    }
+    if (plan.keep) {
+        ctx->refit_links = std::move(plan.refit_links);
+        ctx->refit_dups = std::move(plan.refit_dups);
+        ctx->refit_level_first = std::move(plan.refit_level_first);
+        ctx->refit_front_first = std::move(plan.refit_front_first);
+        ctx->refit_vertex_bytes = vertex_bytes;
+        ctx->refit_bvh_bytes = bvh_bytes;
     }
     ctx->n_nodes = hs.n_nodes;
     ctx->n_tris = hs.n_tris;
     ctx->max_depth = hs.max_depth;
     ctx->has_scene = true;
-    ctx->refit_held = keep;
-    ctx->refit_device_held = keep && front;
+    ctx->refit_held = plan.keep;
+    ctx->refit_device_held = plan.keep && plan.front;
     ++ctx->scene_gen;
     for (PerDevice& p : ctx->dev) p.temporal_valid = false;   // rt_render_temporal starts a new sequence
     for (PerDevice& p : ctx->dev) p.samples_held = 0;         // and rt_render_samples a new sum
-    free_host_scene(&hs);
     return RT_OK;
 }
 
@@ -3841,15 +3477,24 @@ int rt_unpack_rgb(const void* d_rgb, void* d_rgba, size_t n_px, void* stream) {
     return RT_OK;
 }
 
+// The validation of an upload for `who`; *reach = the bytes of the nodes the root's subtree holds.
+static int validated_reach(const void* vertices, size_t vertex_bytes, const void* materials, size_t material_bytes,
+                           const void* bvh_nodes, size_t bvh_bytes, const char* who, size_t* reach) {
+    HostScene hs;
+    std::string err;
+    const int rc = build_host_scene(vertices, vertex_bytes, materials, material_bytes, bvh_nodes, bvh_bytes, &hs, &err);
+    if (rc != RT_OK) set_error("%s: %s", who, err.c_str());
+    *reach = (size_t)hs.end * RT_NODE_RECORD_BYTES;
+    return rc;
+}
+
 int rt_accel_records(const void* vertices, size_t vertex_bytes, const void* materials, size_t material_bytes,
                      const void* bvh_nodes, size_t bvh_bytes, int n_layouts, uint32_t* out_words, size_t cap_words,
                      size_t* n_words, int32_t info[8]) {
-    HostScene hs;
-    const char* err = nullptr;
-    int rc = build_host_scene(vertices, vertex_bytes, materials, material_bytes, bvh_nodes, bvh_bytes, &hs, &err);
-    if (rc != RT_OK) { set_error("rt_accel_records: %s", err); return rc; }
-    const size_t reach = (size_t)hs.end * RT_NODE_RECORD_BYTES;    // the root's subtree only
-    free_host_scene(&hs);
+    size_t reach = 0;
+    int rc = validated_reach(vertices, vertex_bytes, materials, material_bytes, bvh_nodes, bvh_bytes, "rt_accel_records",
+                             &reach);
+    if (rc != RT_OK) return rc;
     AccelHost ah;
     std::string msg;
     const int nl = n_layouts & ~(RT_ACCEL_FORMAT_HALF | RT_ACCEL_FORMAT_WIDE);
@@ -3896,12 +3541,10 @@ int rt_accel_refit_records(uint32_t* words_inout, size_t n_words, int n_layouts,
     // the validation of an upload; the materials take no part (any buffer that covers the triangles)
     const size_t n_tris = vertex_bytes < RT_VERTEX_RECORD_BYTES ? 0 : vertex_bytes / RT_VERTEX_RECORD_BYTES;
     std::vector<float> mats(4 * std::max<size_t>(n_tris, 1), 0.f);
-    HostScene hs;
-    const char* err = nullptr;
-    int rc = build_host_scene(vertices, vertex_bytes, mats.data(), mats.size() * 4, bvh_nodes, bvh_bytes, &hs, &err);
-    if (rc != RT_OK) { set_error("rt_accel_refit_records: %s", err); return rc; }
-    const size_t reach = (size_t)hs.end * RT_NODE_RECORD_BYTES;    // the root's subtree only
-    free_host_scene(&hs);
+    size_t reach = 0;
+    const int rc = validated_reach(vertices, vertex_bytes, mats.data(), mats.size() * 4, bvh_nodes, bvh_bytes,
+                                   "rt_accel_refit_records", &reach);
+    if (rc != RT_OK) return rc;
     std::string msg;
     if (accel_refit_records(words_inout, n_layouts, (int)slots, vertices, n_tris * RT_VERTEX_RECORD_BYTES, bvh_nodes,
                             reach, &msg) != 0) {
@@ -3914,12 +3557,11 @@ int rt_accel_refit_records(uint32_t* words_inout, size_t n_words, int n_layouts,
 int rt_scene_validate(const void* vertices, size_t vertex_bytes, const void* materials, size_t material_bytes,
                       const void* bvh_nodes, size_t bvh_bytes, size_t* n_nodes, int* max_depth) {
     HostScene hs;
-    const char* err = nullptr;
-    int rc = build_host_scene(vertices, vertex_bytes, materials, material_bytes, bvh_nodes, bvh_bytes, &hs, &err);
-    if (rc != RT_OK) { set_error("rt_scene_validate: %s", err); return rc; }
+    std::string err;
+    const int rc = build_host_scene(vertices, vertex_bytes, materials, material_bytes, bvh_nodes, bvh_bytes, &hs, &err);
+    if (rc != RT_OK) { set_error("rt_scene_validate: %s", err.c_str()); return rc; }
     if (n_nodes) *n_nodes = (size_t)hs.end;
     if (max_depth) *max_depth = hs.max_depth;
-    free_host_scene(&hs);
     return RT_OK;
 }
 

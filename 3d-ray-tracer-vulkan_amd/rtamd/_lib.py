@@ -55,9 +55,9 @@ EXPORTED = (
 # "src=" field is the first 16 hex digits of SHA-256 over them concatenated.
 BUILD_SOURCES = ("csrc/rt_trace.hip", "csrc/rt_runtime.hip", "csrc/rt_learn.hip", "csrc/rt_wire.hip",
                  "csrc/rt_filter.hip", "csrc/rt_temporal.hip", "csrc/rt_samples.hip", "csrc/rt_refit.hip", "csrc/rt_rngtable.hip",
-                 "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/rt_internal.h", "csrc/rt_pixel.h",
+                 "csrc/scene_build.cpp", "csrc/accel_build.cpp", "csrc/scene_plan.cpp", "csrc/rt_internal.h", "csrc/rt_pixel.h",
                  "csrc/accel_build.h", "csrc/temporal_motion_host.h", "csrc/refit_levels_host.h", "csrc/rt_rng.h",
-                 "csrc/rng_table_host.h", "../include/rtamd.h")
+                 "csrc/rng_table_host.h", "csrc/scene_plan.h", "../include/rtamd.h")
 
 
 def source_hash() -> str:

@@ -34,6 +34,11 @@ moved and the original triangles:
   same_records     every device array after the last device update equals the
                    arrays after the host path's update of the same triangles
 
+--upload (needs a GPU): for each config, the host wall time of --uploads calls of
+rt_upload_scene after one warm-up, with option refit 0 and then 1, and the
+library's build id (RTAMD_LIB_PATH chooses the library: profiles/scene_plan
+alternates two of them).
+
 --quality (CPU only): node visits per segment of the accel walk's CPU model
 (oracle/rt_accel_model.c) over config 3 after deformations (b), (c) and (f),
 on the refitted records and on a fresh rt_accel_records of the moved scene:
@@ -208,6 +213,27 @@ def bench_device(k, args):
         emit(rec, args.out)
 
 
+def bench_upload(k, args):
+    """--upload: the wall time of rt_upload_scene alone, with option refit 0 and 1."""
+    import rtamd
+    from rtamd import build_buffers, configs, triangles_of
+    tv, mats = triangles_of(configs.get(k).scene)
+    built = build_buffers(tv, mats, 1)
+    with rtamd.Renderer((0,)) as r:
+        r.set_option("accel", args.accel)
+        for refit in (0, 1):
+            r.set_option("refit", refit)
+            r.upload_scene(built)               # warm-up
+            up = []
+            for _ in range(args.uploads):
+                t0 = time.perf_counter()
+                r.upload_scene(built)
+                up.append((time.perf_counter() - t0) * 1e3)
+            emit({"what": "upload_wall", "library": rtamd.lib().rt_build_id().decode(), "config": k,
+                  "accel_used": r.get_option("accel_used"), "refit": refit, "flat_triangles": built.triangle_count,
+                  "upload_ms": [round(x, 2) for x in up], "upload_median_ms": round(statistics.median(up), 2)}, args.out)
+
+
 def quality(args):
     import numpy as np
     import refit_ref as R
@@ -250,6 +276,7 @@ def main():
     ap.add_argument("--accel", type=int, default=8)
     ap.add_argument("--quality", action="store_true")
     ap.add_argument("--device", action="store_true", help="time rt_update_geometry_device beside the host path")
+    ap.add_argument("--upload", action="store_true", help="time rt_upload_scene alone, with option refit 0 and 1")
     ap.add_argument("--row-step", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refit", "refit_bench.jsonl"))
     args = ap.parse_args()
@@ -262,7 +289,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("refit_bench.py needs a GPU for the timings (--quality runs without one)")
     for k in (int(x) for x in args.configs.split(",")):
-        (bench_device if args.device else bench_config)(k, args)
+        (bench_upload if args.upload else bench_device if args.device else bench_config)(k, args)
 
 
 if __name__ == "__main__":
