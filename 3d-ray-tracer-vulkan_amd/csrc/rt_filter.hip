@@ -23,6 +23,10 @@
 //       3x3 binomial window (always at step 1), and v is filtered along with
 //       the colour (weights squared).  §4i's count of passes, n read from the
 //       history.
+// A fourth policy, Albedo (rt_denoise_albedo_device, §4p), is Radiance on the
+// illumination: its pass 0 divides the colour by the first-hit albedo buffer
+// (written by first_hit_albedo below, rt_albedo_device), its last pass
+// multiplies the centre's result back, and the passes between are Radiance's.
 //
 // Every pass but the last writes its filter's record into the other half of
 // the caller's workspace; the last writes sqrt(c) and the RGBA8 pixels.  All
@@ -118,7 +122,10 @@ struct Sums {
 // is_tap      : whether a record inside the frame counts
 // fourth      : the fourth word stored with the colour (r, g, b); w = the centre's own, or with kFiltersW
 //               the filtered one
+// Args        : the kernels' first argument, PassArgs or a struct derived from it
+// display     : what the last pass does to the centre's colour before the display store
 struct Radiance {
+    using Args = PassArgs;
     static constexpr bool  kLumPlane = false;
     static constexpr float kOutsideW = 0.0f;
     static constexpr bool  kTiledStep1 = false;
@@ -154,9 +161,11 @@ struct Radiance {
     __device__ static __forceinline__ float weight(float hn, float4) { return hn; }
     __device__ static __forceinline__ bool is_tap(float4 q0, float4) { return __float_as_int(q0.y) >= 0; }
     __device__ static __forceinline__ float fourth(float r, float g, float b, float) { return lum_of(r, g, b); }
+    __device__ static __forceinline__ void display(const PassArgs&, size_t, float&, float&, float&) {}
 };
 
 struct History {
+    using Args = PassArgs;
     static constexpr bool  kLumPlane = true;
     static constexpr float kOutsideW = 0.0f;       // without a sample
     static constexpr bool  kTiledStep1 = false;
@@ -188,9 +197,11 @@ struct History {
     __device__ static __forceinline__ float weight(float hn, float4 cq) { return hn * cq.w; }
     __device__ static __forceinline__ bool is_tap(float4 q0, float4 cq) { return live(q0.y, cq.w); }
     __device__ static __forceinline__ float fourth(float, float, float, float n) { return n; }
+    __device__ static __forceinline__ void display(const PassArgs&, size_t, float&, float&, float&) {}
 };
 
 struct Variance {
+    using Args = PassArgs;
     static constexpr bool  kLumPlane = true;
     static constexpr float kOutsideW = -1.0f;      // not a tap
     static constexpr bool  kTiledStep1 = true;
@@ -223,14 +234,54 @@ struct Variance {
     __device__ static __forceinline__ float weight(float hn, float4) { return hn; }
     __device__ static __forceinline__ bool is_tap(float4, float4 cq) { return cq.w >= 0.0f; }
     __device__ static __forceinline__ float fourth(float, float, float, float v) { return v; }
+    __device__ static __forceinline__ void display(const PassArgs&, size_t, float&, float&, float&) {}
+};
+
+// Albedo (rt_denoise_albedo_device, §4p): the Radiance filter on the illumination.  Pass 0 (kDivides) reads a
+// pixel or tap q as c = g * g and divides it per channel by d_q, the first three words of q's albedo record;
+// the last pass (kMultiplies) multiplies the centre's result by d_p before the display store; a one-pass filter
+// does both.  The passes between are Radiance's own kernels, and each of the three is an instantiation of its
+// own: one kernel doing both and choosing at run time, used for every pass, ran the whole 4-pass filter 5.8 %
+// over the colour filter's instead of 2.6 %.  The albedo buffer is a kernel argument behind
+// PassArgs' own, so the other filters' kernels keep their argument layout.
+struct AlbedoPassArgs : PassArgs {
+    const float4* albedo;     // (d.rgb, any) per pixel
+};
+template <bool kDivides, bool kMultiplies>
+struct Albedo : Radiance {
+    using Args = AlbedoPassArgs;
+    __device__ static __forceinline__ float4 load(const Args& a, size_t q) {
+        if constexpr (kDivides) {                  // pass 0: a.side is the radiance
+            const float gr = a.side[3 * q + 0], gg = a.side[3 * q + 1], gb = a.side[3 * q + 2];
+            const float4 d = a.albedo[q];
+            const float r = (gr * gr) / d.x, g = (gg * gg) / d.y, b = (gb * gb) / d.z;
+            return make_float4(r, g, b, lum_of(r, g, b));
+        } else {
+            return Radiance::load(a, q);
+        }
+    }
+    __device__ static __forceinline__ float4 load_tap(const Args& a, size_t q, float4& q0, float4& q1) {
+        q0 = a.hits[2 * q];
+        q1 = a.hits[2 * q + 1];
+        return load(a, q);
+    }
+    __device__ static __forceinline__ void display(const Args& a, size_t p, float& r, float& g, float& b) {
+        if constexpr (kMultiplies) {
+            const float4 d = a.albedo[p];
+            r = r * d.x;
+            g = g * d.y;
+            b = b * d.z;
+        }
+    }
 };
 
 template <class F>
-__device__ __forceinline__ void store_px(const PassArgs& a, size_t p, float r, float g, float b, float w) {
+__device__ __forceinline__ void store_px(const typename F::Args& a, size_t p, float r, float g, float b, float w) {
     if (a.out_c) {
         a.out_c[p] = make_float4(r, g, b, F::fourth(r, g, b, w));
         return;
     }
+    F::display(a, p, r, g, b);
     store_display(a.out_rgba, a.out_rad, p, r, g, b);
 }
 
@@ -252,7 +303,7 @@ __device__ __forceinline__ void tap(Sums& s, const Guide& c, const PassArgs& a, 
 }
 
 template <class F>
-__device__ __forceinline__ void finish(const PassArgs& a, size_t p, const Sums& s, float4 cp) {
+__device__ __forceinline__ void finish(const typename F::Args& a, size_t p, const Sums& s, float4 cp) {
     const bool ok = s.ws > 0.0f;                   // NaN or zero: the pixel passes through
     float w = cp.w;
     if constexpr (F::kFiltersW) w = ok ? s.vs / (s.ws * s.ws) : cp.w;
@@ -261,7 +312,7 @@ __device__ __forceinline__ void finish(const PassArgs& a, size_t p, const Sums& 
 
 // ---- plain: one lane per pixel, 64 x 4 pixels per workgroup, taps from global memory
 template <class F>
-__global__ __launch_bounds__(256, 4) void atrous_plain(PassArgs a, int tiles_x) {
+__global__ __launch_bounds__(256, 4) void atrous_plain(typename F::Args a, int tiles_x) {
     const int bx = (int)(blockIdx.x % (unsigned)tiles_x), by = (int)(blockIdx.x / (unsigned)tiles_x);
     const int x = bx * 64 + (int)(threadIdx.x & 63u), y = by * 4 + (int)(threadIdx.x >> 6);
     if (x >= a.W || y >= a.H) return;
@@ -316,7 +367,7 @@ __global__ __launch_bounds__(256, 4) void atrous_plain(PassArgs a, int tiles_x) 
 constexpr int kTileX = 32, kTileY = 8, kHaloX = kTileX + 4, kHaloY = kTileY + 4;
 
 template <class F>
-__global__ __launch_bounds__(256, 4) void atrous_tiled(PassArgs a, int tiles_x) {
+__global__ __launch_bounds__(256, 4) void atrous_tiled(typename F::Args a, int tiles_x) {
     __shared__ float4 s_c[kHaloX * kHaloY], s_h0[kHaloX * kHaloY], s_h1[kHaloX * kHaloY];
     __shared__ float s_lum[F::kLumPlane ? kHaloX * kHaloY : 1];
     const int step = F::kTiledStep1 ? 1 : a.step;
@@ -492,8 +543,40 @@ constexpr bool kTiledByStep[3][6] = {{true, true, true, false, false, false},
 using PassKernel = void (*)(PassArgs, int);
 constexpr PassKernel kPlain[3] = {atrous_plain<Radiance>, atrous_plain<History>, atrous_plain<Variance>};
 constexpr PassKernel kTiled[3] = {atrous_tiled<Radiance>, atrous_tiled<History>, atrous_tiled<Variance>};
+// the albedo form's pass 0, last pass and only pass, [multiplies][divides] (neither: Radiance's kernels)
+using AlbedoKernel = void (*)(AlbedoPassArgs, int);
+constexpr AlbedoKernel kAlbedoPlain[2][2] = {{nullptr, atrous_plain<Albedo<true, false>>},
+                                             {atrous_plain<Albedo<false, true>>, atrous_plain<Albedo<true, true>>}};
+constexpr AlbedoKernel kAlbedoTiled[2][2] = {{nullptr, atrous_tiled<Albedo<true, false>>},
+                                             {atrous_tiled<Albedo<false, true>>, atrous_tiled<Albedo<true, true>>}};
+
+// ---- the first-hit albedo buffer (rt_albedo_device, §4p)
+// a channel the filter may divide by: 2^-10 <= a <= 2^10, else 1 (a NaN fails both comparisons)
+__device__ __forceinline__ float divisor_of(float a) { return (a >= 0x1p-10f && a <= 0x1p10f) ? a : 1.0f; }
+
+// One lane per pixel: (d.rgb, type) of the triangle the pixel's hit record names, (1, 1, 1, -1) where it
+// names none of the scene's n_flat.  Reads the record's tri alone.
+__global__ __launch_bounds__(256) void first_hit_albedo(const int* hits, const float4* mats, unsigned n_flat, float4* out,
+                                                        size_t px) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= px) return;
+    const unsigned tri = (unsigned)hits[8 * p + 1];
+    float4 r = make_float4(1.0f, 1.0f, 1.0f, -1.0f);
+    if (tri < n_flat) {
+        const float4 m = mats[(size_t)kShadeStride * tri];
+        r = make_float4(divisor_of(m.x), divisor_of(m.y), divisor_of(m.z), m.w);
+    }
+    out[p] = r;
+}
 
 }  // namespace
+
+hipError_t launch_albedo(const float4* hits, const float4* mats, unsigned n_flat, float4* out, size_t px,
+                         hipStream_t stream) {
+    hipLaunchKernelGGL(first_hit_albedo, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const int*>(hits), mats, n_flat, out, px);
+    return hipGetLastError();
+}
 
 hipError_t launch_filter(const FilterArgs& d, hipStream_t stream) {
     const size_t px = (size_t)d.width * (size_t)d.height;
@@ -539,7 +622,17 @@ hipError_t launch_filter(const FilterArgs& d, hipStream_t stream) {
         bool tiled = d.form == 2 || (d.form == 0 && kTiledByStep[d.kind][i]);
         if (variance && i > 0) tiled = false;                        // its 3x3 window leaves a class's tile
         if (tiled_blocks > 0x7FFFFFFFull) tiled = false;             // past a 1-D grid: the plain form
-        if (tiled)
+        if (d.albedo && (i == 0 || last)) {                          // (kind Radiance: its table, its forms)
+            AlbedoPassArgs b;
+            static_cast<PassArgs&>(b) = a;
+            b.albedo = d.albedo;
+            if (tiled)
+                hipLaunchKernelGGL(kAlbedoTiled[last][i == 0], dim3((unsigned)tiled_blocks), dim3(256), 0, stream, b,
+                                   (int)ttx);
+            else
+                hipLaunchKernelGGL(kAlbedoPlain[last][i == 0], dim3((unsigned)(ptx * pty)), dim3(256), 0, stream, b,
+                                   (int)ptx);
+        } else if (tiled)
             hipLaunchKernelGGL(kTiled[d.kind], dim3((unsigned)tiled_blocks), dim3(256), 0, stream, a, (int)ttx);
         else
             hipLaunchKernelGGL(kPlain[d.kind], dim3((unsigned)(ptx * pty)), dim3(256), 0, stream, a, (int)ptx);

@@ -292,8 +292,8 @@ hipError_t wire_pack(const void* rgba, void* rgb, size_t n_px, hipStream_t s);
 hipError_t wire_unpack(const void* rgb, void* rgba, size_t n_px, hipStream_t s);
 
 // rt_filter.hip: an a-trous filter's passes (rtamd.h rt_denoise_device,
-// rt_denoise_history_device and rt_denoise_variance_device; DESIGN.md §4g, §4i,
-// §4j), enqueued on `stream`; validated arguments, nothing allocated.
+// rt_denoise_albedo_device, rt_denoise_history_device and
+// rt_denoise_variance_device), enqueued on `stream`; validated arguments, nothing allocated.
 enum FilterKind { kFilterRadiance = 0, kFilterHistory = 1, kFilterVariance = 2 };
 struct FilterArgs {
     FilterKind    kind;
@@ -315,8 +315,16 @@ struct FilterArgs {
     int           only_pass;    // option denoise_pass: -1 = every pass (Variance: behind the estimate),
                                 //   i = pass i alone (timing)
     int           stage;        // Variance, option variance_stage: -1 = everything, 0 = the estimate alone (timing)
+    // Radiance on the illumination (rtamd.h rt_denoise_albedo_device): the albedo buffer,
+    // (d.rgb, any) per pixel; null = the colour is filtered as it is
+    const float4* albedo = nullptr;
 };
 hipError_t launch_filter(const FilterArgs& d, hipStream_t stream);
+// The first-hit albedo buffer (rtamd.h rt_albedo_device): out[p] = (d.rgb, type) of the
+// flattened triangle hits[p] names among the scene's n_flat material records `mats` (kShadeStride float4
+// apart), (1, 1, 1, -1) where it names none; px pixels.
+hipError_t launch_albedo(const float4* hits, const float4* mats, unsigned n_flat, float4* out, size_t px,
+                         hipStream_t stream);
 
 // rt_temporal.hip: the temporal accumulation's one kernel (rtamd.h
 // rt_temporal_device and rt_temporal_moments_device),

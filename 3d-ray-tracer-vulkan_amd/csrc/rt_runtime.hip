@@ -167,9 +167,11 @@ struct PerDevice {
     size_t       query_cap = 0;      // bytes
     int          ref_root_leaf = 0;
     // rt_render_denoised: one allocation holding the frame's radiance, hit
-    // records, filter workspace and filtered outputs, grown on demand
+    // records, filter workspace and filtered outputs (and, with option
+    // denoise_albedo, the albedo buffer behind them), grown on demand
     char*        d_denoise = nullptr;
     size_t       denoise_cap = 0;    // bytes
+    int          albedo_used = 0;    // the last rt_render_denoised ran the albedo form (option "denoise_albedo_used")
     // rt_render_temporal: one allocation holding the frame's radiance, the two
     // history / hit buffer pairs that ping-pong, the outputs and (with a
     // spatial filter) its workspace, grown on demand; and the sequence's state:
@@ -314,6 +316,8 @@ struct rt_ctx {
     int  denoise_kernel = 0;       // rt_denoise_device: 0 = per step size the form measured faster, 1 = the
                                    //   plain form, 2 = the tiled form (rt_filter.hip; same results)
     int  denoise_pass = -1;        // rt_denoise_device: i >= 0 = enqueue pass i alone (tools/denoise_bench.py)
+    int  denoise_albedo = 0;       // rt_render_denoised: 1 = rt_albedo_device, then rt_denoise_albedo_device in
+                                   //   place of rt_denoise_device
     int  temporal_tile = 0;        // rt_temporal_device: 0 = the lane mapping measured faster, 1 = a wave on 64
                                    //   pixels of a row, 2 = on a 16x4 tile (rt_temporal.hip; same results)
     int  variance_stage = -1;      // rt_denoise_variance_device: 0 = enqueue the estimate alone (tools/variance_bench.py)
@@ -2184,21 +2188,24 @@ static int check_variance_params(const rt_variance_params* q, const char* fn) {
     return RT_OK;
 }
 
-// rt_denoise_device (d_in = the render's radiance, 12 B per pixel), rt_denoise_history_device (d_in = a
-// history buffer, 16 B per pixel) and rt_denoise_variance_device (d_in = a history buffer, d_mom = its
-// moments, 8 B per pixel; vparams in place of params): the same checks, workspace and passes' timing.
+// rt_denoise_device (d_in = the render's radiance, 12 B per pixel), rt_denoise_albedo_device (the same with
+// `albedo`: d_albedo = the albedo buffer, 16 B per pixel), rt_denoise_history_device (d_in = a history
+// buffer, 16 B per pixel) and rt_denoise_variance_device (d_in = a history buffer, d_mom = its moments, 8 B
+// per pixel; vparams in place of params): the same checks, workspace and passes' timing.
 static int denoise_device(const char* fn, FilterKind kind, rt_ctx* ctx, int width, int height, const void* d_in,
                           const void* d_mom, const rt_hit* d_hits, const rt_denoise_params* params,
                           const rt_variance_params* vparams, void* d_workspace, void* d_out_rgba,
-                          float* d_out_radiance, void* stream, double* ms) {
+                          float* d_out_radiance, void* stream, double* ms, bool albedo = false,
+                          const void* d_albedo = nullptr) {
     const bool variance = kind == kFilterVariance;
     if (!ctx) { set_error("%s: null context or buffer", fn); return RT_ERR_INVALID_ARG; }
     const size_t ws_bytes = rt_denoise_workspace_bytes(width, height);
     const size_t px = ws_bytes / 32;
-    const Buf bufs[6] = {
+    const Buf bufs[7] = {
         {d_in, px * (kind == kFilterRadiance ? 12 : 16), kind == kFilterRadiance ? 4u : 16u,
          kind == kFilterRadiance ? "d_radiance" : "d_hist", kBufIn, false},
         {d_mom, px * 8, 8, "d_mom", kBufIn, !variance},
+        {d_albedo, px * 16, 16, "d_albedo", kBufIn, !albedo},
         {d_hits, px * 32, 16, "d_hits", kBufIn, false},
         {d_workspace, ws_bytes, 16, "d_workspace", kBufWorkspace, false},
         {d_out_rgba, px * 4, 4, "d_out_rgba", kBufOut, true},
@@ -2216,7 +2223,7 @@ static int denoise_device(const char* fn, FilterKind kind, rt_ctx* ctx, int widt
         if (params) q = *params;
         if (int rc = check_denoise_params(&q, fn)) return rc;
     }
-    if (int rc = check_buffers(fn, "context or buffer", bufs, 6)) return rc;
+    if (int rc = check_buffers(fn, "context or buffer", bufs, 7)) return rc;
     PerDevice& p = ctx->dev[0];
     RT_HIP_CHECK(hipSetDevice(p.device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2226,6 +2233,7 @@ static int denoise_device(const char* fn, FilterKind kind, rt_ctx* ctx, int widt
     d.radiance = kind == kFilterRadiance ? static_cast<const float*>(d_in) : nullptr;
     d.hist = kind == kFilterRadiance ? nullptr : static_cast<const float4*>(d_in);
     d.mom = static_cast<const float2*>(d_mom);
+    d.albedo = static_cast<const float4*>(d_albedo);
     d.hits = reinterpret_cast<const float4*>(d_hits);
     d.workspace = static_cast<float4*>(d_workspace);
     d.out_rgba = static_cast<uchar4*>(d_out_rgba);
@@ -2248,6 +2256,32 @@ int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radianc
                       void* stream, double* ms) {
     return denoise_device("rt_denoise_device", kFilterRadiance, ctx, width, height, d_radiance, nullptr, d_hits, params,
                           nullptr, d_workspace, d_out_rgba, d_out_radiance, stream, ms);
+}
+
+int rt_denoise_albedo_device(rt_ctx* ctx, int width, int height, const float* d_radiance, const rt_hit* d_hits,
+                             const void* d_albedo, const rt_denoise_params* params, void* d_workspace,
+                             void* d_out_rgba, float* d_out_radiance, void* stream, double* ms) {
+    return denoise_device("rt_denoise_albedo_device", kFilterRadiance, ctx, width, height, d_radiance, nullptr, d_hits,
+                          params, nullptr, d_workspace, d_out_rgba, d_out_radiance, stream, ms, true, d_albedo);
+}
+
+// Like the filter, it works on the caller's buffers and the uploaded scene's material records alone.
+int rt_albedo_device(rt_ctx* ctx, int width, int height, const rt_hit* d_hits, void* d_albedo, void* stream,
+                     double* ms) {
+    const char* const fn = "rt_albedo_device";
+    if (!ctx) { set_error("%s: null context or buffer", fn); return RT_ERR_INVALID_ARG; }
+    if (!ctx->has_scene) { set_error("%s: no scene uploaded", fn); return RT_ERR_NO_SCENE; }
+    const size_t px = rt_denoise_workspace_bytes(width, height) / 32;
+    if (px == 0) { set_error("%s: bad frame size %dx%d", fn, width, height); return RT_ERR_INVALID_ARG; }
+    const Buf bufs[2] = {{d_hits, px * 32, 16, "d_hits", kBufIn, false}, {d_albedo, px * 16, 16, "d_albedo", kBufOut, false}};
+    if (int rc = check_buffers(fn, "context or buffer", bufs, 2)) return rc;
+    PerDevice& p = ctx->dev[0];
+    RT_HIP_CHECK(hipSetDevice(p.device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ms) RT_HIP_CHECK(hipEventRecord(p.ev0, s));
+    RT_HIP_CHECK(launch_albedo(reinterpret_cast<const float4*>(d_hits), p.scene.mats, (unsigned)p.scene.n_tris,
+                               static_cast<float4*>(d_albedo), px, s));
+    return ms ? elapsed_ms(p, s, ms) : RT_OK;
 }
 
 int rt_denoise_history_device(rt_ctx* ctx, int width, int height, const void* d_hist, const rt_hit* d_hits,
@@ -2283,11 +2317,12 @@ int rt_render_denoised(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int hei
         if (int rq = check_denoise_params(params, "rt_render_denoised")) return rq;
     RT_HIP_CHECK(hipSetDevice(p.device));
     // radiance (12 B), hit records (32 B), workspace (32 B), RGBA8 (4 B), filtered radiance (12 B) per
-    // pixel, each part on a 256-byte boundary
+    // pixel, each part on a 256-byte boundary; with option denoise_albedo the albedo buffer (16 B) behind them
+    const bool albedo = ctx->denoise_albedo != 0;
     const size_t px = (size_t)width * (size_t)height;
     const auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
     const size_t o_hits = up(px * 12), o_ws = o_hits + up(px * 32), o_rgba = o_ws + up(px * 32),
-                 o_rad = o_rgba + up(px * 4), total = o_rad + up(px * 12);
+                 o_rad = o_rgba + up(px * 4), o_alb = o_rad + up(px * 12), total = o_alb + (albedo ? up(px * 16) : 0);
     if (total > p.denoise_cap) {
         if (p.d_denoise) {
             RT_HIP_CHECK(hipStreamSynchronize(p.stream));   // (the call is synchronous: nothing in flight)
@@ -2310,12 +2345,22 @@ int rt_render_denoised(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int hei
     if (rc) return rc;
     rc = rt_render_hits_device(ctx, cam, width, height, 0, 0, width, height, 0, d_hits, p.stream, nullptr);
     if (rc) return rc;
-    double dn_ms = 0.0;
-    rc = rt_denoise_device(ctx, width, height, d_rad, d_hits, params, p.d_denoise + o_ws, p.d_denoise + o_rgba,
-                           out_radiance ? reinterpret_cast<float*>(p.d_denoise + o_rad) : nullptr, p.stream,
-                           stats ? &dn_ms : nullptr);
+    double dn_ms = 0.0, al_ms = 0.0;
+    float* const d_out_rad = out_radiance ? reinterpret_cast<float*>(p.d_denoise + o_rad) : nullptr;
+    p.albedo_used = 0;
+    if (albedo) {
+        rc = rt_albedo_device(ctx, width, height, d_hits, p.d_denoise + o_alb, p.stream, stats ? &al_ms : nullptr);
+        if (rc) return rc;
+        rc = rt_denoise_albedo_device(ctx, width, height, d_rad, d_hits, p.d_denoise + o_alb, params,
+                                      p.d_denoise + o_ws, p.d_denoise + o_rgba, d_out_rad, p.stream,
+                                      stats ? &dn_ms : nullptr);
+        if (rc == RT_OK) p.albedo_used = 1;
+    } else {
+        rc = rt_denoise_device(ctx, width, height, d_rad, d_hits, params, p.d_denoise + o_ws, p.d_denoise + o_rgba,
+                               d_out_rad, p.stream, stats ? &dn_ms : nullptr);
+    }
     if (rc) return rc;
-    if (stats) stats->ms += dn_ms;
+    if (stats) stats->ms += dn_ms + al_ms;
     RT_HIP_CHECK(hipMemcpyAsync(out_rgba, p.d_denoise + o_rgba, px * 4, hipMemcpyDeviceToHost, p.stream));
     if (out_radiance)
         RT_HIP_CHECK(hipMemcpyAsync(out_radiance, p.d_denoise + o_rad, px * 12, hipMemcpyDeviceToHost, p.stream));
@@ -3242,6 +3287,7 @@ static const Option kOptions[] = {
     in_range("wave_tile", &rt_ctx::wave_tile, -1, 3),
     in_range("denoise_kernel", &rt_ctx::denoise_kernel, 0, 2),
     in_range("denoise_pass", &rt_ctx::denoise_pass, -1, 5),
+    one_of("denoise_albedo", &rt_ctx::denoise_albedo, 0, 1),
     in_range("temporal_tile", &rt_ctx::temporal_tile, 0, 2),
     one_of("temporal_motion", &rt_ctx::temporal_motion, 0, 1),
     in_range("variance_stage", &rt_ctx::variance_stage, -1, 0),
@@ -3298,6 +3344,7 @@ int rt_get_option(rt_ctx* ctx, const char* name, int64_t* value) {
     else if (is("refit_bytes")) *value = p ? (int64_t)p->refit_bytes : 0;
     else if (is("refit_device_used")) *value = ctx->refit_device_held ? 1 : 0;
     else if (is("temporal_motion_used")) *value = p ? p->motion_used : 0;
+    else if (is("denoise_albedo_used")) *value = p ? p->albedo_used : 0;
     else if (is("leaf_align_used")) *value = p ? p->scene.padded : 0;
     else if (is("heavy_pixels_used")) *value = p ? p->last_heavy_px : 0;
     else if (is("heavy_tiles_used")) *value = p ? p->last_heavy : 0;

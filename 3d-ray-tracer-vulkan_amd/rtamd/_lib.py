@@ -40,6 +40,7 @@ EXPORTED = (
     "rt_build_id", "rt_render_batch_rect_device", "rt_render_batch_runs_device",
     "rt_query_rays_device", "rt_query_rays", "rt_render_hits_device", "rt_pick", "rt_build_scene_map",
     "rt_denoise_default_params", "rt_denoise_workspace_bytes", "rt_denoise_device", "rt_render_denoised",
+    "rt_albedo_device", "rt_denoise_albedo_device",
     "rt_temporal_default_params", "rt_temporal_camera_basis", "rt_temporal_device", "rt_render_temporal",
     "rt_denoise_history_device", "rt_render_temporal_adaptive",
     "rt_temporal_moments_device", "rt_variance_default_params", "rt_denoise_variance_device",
@@ -254,6 +255,9 @@ def lib() -> C.CDLL:
                 "rt_denoise_device": (i32, [vp, i32, i32, vp, vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, dp]),
                 "rt_render_denoised": (i32, [vp, C.POINTER(CameraUBO), i32, i32, i32, C.POINTER(DenoiseParams), vp, vp,
                                              C.POINTER(Stats)]),
+                "rt_albedo_device": (i32, [vp, i32, i32, vp, vp, vp, dp]),
+                "rt_denoise_albedo_device": (i32, [vp, i32, i32, vp, vp, vp, C.POINTER(DenoiseParams), vp, vp, vp, vp,
+                                                   dp]),
                 "rt_temporal_default_params": (None, [C.POINTER(TemporalParams)]),
                 "rt_temporal_camera_basis": (i32, [C.POINTER(CameraUBO), fp]),
                 "rt_temporal_device": (i32, [vp, i32, i32, C.POINTER(CameraUBO), vp, vp, C.POINTER(CameraUBO), vp, vp,

@@ -291,21 +291,29 @@ class Renderer:
 
     def denoise_device(self, width: int, height: int, d_radiance: int, d_hits: int, d_workspace: int,
                        d_out_rgba: Optional[int] = None, d_out_radiance: Optional[int] = None,
-                       params: Optional[DenoiseParams] = None, stream: Optional[int] = None, ms: bool = False):
+                       params: Optional[DenoiseParams] = None, stream: Optional[int] = None, ms: bool = False,
+                       d_albedo: int = 0):
         """Enqueue the edge-avoiding filter of one whole frame between device
         buffers (raw device pointers; rt_denoise_device) on a HIP stream
         handle; asynchronous unless ms, which waits and returns the passes'
-        device time in milliseconds."""
+        device time in milliseconds.  A non-zero d_albedo (albedo_device's
+        buffer) filters the illumination instead (rt_denoise_albedo_device)."""
         t = C.c_double() if ms else None
-        check(lib().rt_denoise_device(self._ctx, width, height, d_radiance, d_hits,
-                                      C.byref(params) if params is not None else None, d_workspace, d_out_rgba,
-                                      d_out_radiance, stream, C.byref(t) if t is not None else None))
+        q = C.byref(params) if params is not None else None
+        if d_albedo:
+            check(lib().rt_denoise_albedo_device(self._ctx, width, height, d_radiance, d_hits, d_albedo, q, d_workspace,
+                                                 d_out_rgba, d_out_radiance, stream,
+                                                 C.byref(t) if t is not None else None))
+        else:
+            check(lib().rt_denoise_device(self._ctx, width, height, d_radiance, d_hits, q, d_workspace, d_out_rgba,
+                                          d_out_radiance, stream, C.byref(t) if t is not None else None))
         return t.value if t is not None else None
 
-    def denoise(self, radiance, hits, params: Optional[DenoiseParams] = None):
+    def denoise(self, radiance, hits, params: Optional[DenoiseParams] = None, albedo=None):
         """The filter on host arrays: radiance float32 [H, W, 3] (render()'s)
         and HIT_DTYPE records [H, W] (render_hits()'s) in, (rgba uint8
-        [H, W, 4], radiance float32 [H, W, 3]) out."""
+        [H, W, 4], radiance float32 [H, W, 3]) out.  With albedo (float32
+        [H, W, 4], albedo()'s) the illumination is filtered."""
         import torch
         rad = np.ascontiguousarray(radiance, dtype=np.float32)
         h, w = rad.shape[:2]
@@ -313,12 +321,40 @@ class Renderer:
         with torch.cuda.device(self.device_ids[0]):
             d_rad = torch.from_numpy(rad).cuda()
             d_hit = torch.from_numpy(hit.view(np.float32).reshape(h, w, 8)).cuda()
+            d_alb = None
+            if albedo is not None:
+                d_alb = torch.from_numpy(np.ascontiguousarray(albedo, dtype=np.float32).reshape(h, w, 4)).cuda()
             d_ws = torch.empty((2, h, w, 4), dtype=torch.float32, device="cuda")
             o_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda")
             o_rad = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
             self.denoise_device(w, h, d_rad.data_ptr(), d_hit.data_ptr(), d_ws.data_ptr(), o_rgba.data_ptr(),
-                                o_rad.data_ptr(), params, torch.cuda.current_stream().cuda_stream)
+                                o_rad.data_ptr(), params, torch.cuda.current_stream().cuda_stream,
+                                d_albedo=d_alb.data_ptr() if d_alb is not None else 0)
             return o_rgba.cpu().numpy(), o_rad.cpu().numpy()
+
+    def albedo_device(self, width: int, height: int, d_hits: int, d_albedo: int, stream: Optional[int] = 0,
+                      ms: bool = False):
+        """Enqueue the first-hit albedo buffer of a frame's hit records between
+        device buffers (raw 16-byte aligned device pointers; rt_albedo_device)
+        on a HIP stream handle: 4 floats per pixel, (d.rgb, type), (1, 1, 1,
+        -1) without a hit.  Asynchronous unless ms, which waits and returns the
+        kernel's device time in milliseconds."""
+        t = C.c_double() if ms else None
+        check(lib().rt_albedo_device(self._ctx, width, height, d_hits, d_albedo, stream,
+                                     C.byref(t) if t is not None else None))
+        return t.value if t is not None else None
+
+    def albedo(self, hits) -> np.ndarray:
+        """The albedo buffer of HIT_DTYPE records [H, W] (render_hits()'s) on
+        host arrays: float32 [H, W, 4]."""
+        import torch
+        hit = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        h, w = hit.shape
+        with torch.cuda.device(self.device_ids[0]):
+            d_hit = torch.from_numpy(hit.view(np.float32).reshape(h, w, 8)).cuda()
+            d_alb = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
+            self.albedo_device(w, h, d_hit.data_ptr(), d_alb.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            return d_alb.cpu().numpy()
 
     def render_denoised(self, camera, width: int, height: int, max_bounces: int = REFERENCE_MAX_BOUNCES,
                         params: Optional[DenoiseParams] = None, radiance: bool = False, stats: bool = False):

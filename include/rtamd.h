@@ -483,6 +483,57 @@ int rt_denoise_device(rt_ctx* ctx, int width, int height, const float* d_radianc
 int rt_render_denoised(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int height, int max_bounces,
                        const rt_denoise_params* params, uint8_t* out_rgba, float* out_radiance, rt_stats* stats);
 
+/* ------------------------------------------------- albedo, denoise on it -- */
+/* NON-REFERENCE: the first-hit albedo buffer, and the filter above run on the
+ * illumination (the colour divided by that albedo) instead of the colour.
+ * Materials are per triangle, so a flat surface may carry many albedos; the
+ * guides (normal, position, depth) see no edge there and the filter would blur
+ * the texture with the noise.  A path's colour is attenuation x sky and the
+ * first scatter sets attenuation = albedo, so colour / first-hit albedo is
+ * free of the texture.  Added at ABI version 6 without a bump,
+ * as the denoiser was: no existing struct or argument list changed.
+ *
+ * rt_albedo_device: one record of 4 floats per pixel into DEVICE memory
+ * d_albedo (width*height*16 bytes, 16-byte aligned) from the hit records
+ * d_hits (width*height rt_hit, 16-byte aligned, from rt_render_hits_device or
+ * the caller's own) and the uploaded scene's materials, on device 0 of ctx.
+ * With 0 <= tri < the scene's flattened triangles the record is (d.r, d.g,
+ * d.b, type), per channel d = the albedo a where 2^-10 <= a <= 2^10, else
+ * 1.0f (a NaN, negative, zero, denormal or infinite albedo: that channel is
+ * filtered as colour); any other tri (a miss, -2, an index the scene does not
+ * hold) and an empty scene give (1, 1, 1, -1).  Stream and ms as
+ * rt_denoise_device.  Allocates nothing and touches no render, query, denoise
+ * or temporal state ("plain_kernels" included).  RT_ERR_NO_SCENE before any
+ * upload; RT_ERR_INVALID_ARG: a null or misaligned pointer, a bad size
+ * (rt_denoise_workspace_bytes' limit), overlapping buffers. */
+int rt_albedo_device(rt_ctx* ctx, int width, int height, const rt_hit* d_hits, void* d_albedo,
+                     void* stream, double* ms);
+/* rt_denoise_device's contract with two changes, each one binary32 operation
+ * per channel: pass 0 reads a pixel or tap q as c = g * g and then i = c / d_q,
+ * and the luminance, the workspace records and every later pass work on i; the
+ * last pass computes c' = i_filtered * d_p before the sqrt and the RGBA8
+ * store.  A pixel that passes through (no hit, weights summing to zero or NaN)
+ * takes the same two operations, exact with d = 1: a sky pixel keeps its bits.
+ * With iterations 1 the single pass does both.  d = the first three words of
+ * the pixel's record in d_albedo (width*height*16 bytes, 16-byte aligned, not
+ * overlapping any output or the workspace; non-null); the fourth is ignored.
+ * An all-ones buffer gives rt_denoise_device's bits.  Everything else
+ * (workspace, params, outputs, overlaps, errors, stream, ms, the options
+ * "denoise_kernel" and "denoise_pass") is rt_denoise_device's.  The division is
+ * fused into pass 0 and the product into the last pass: no further pass over
+ * the frame, no further workspace.
+ * The division removes the texture exactly when d_radiance is the frame d_hits
+ * describes, that is frame 0's jitter: with option "new_sample" or extensions
+ * bit 4 a sample's jittered primary ray may hit the neighbouring triangle, and
+ * a pixel on an albedo edge is then divided by the neighbour's albedo (on the
+ * checker of DESIGN.md §4p that still measured better than the colour
+ * filter).
+ * rt_render_denoised runs rt_albedo_device and this call in place of
+ * rt_denoise_device with option "denoise_albedo" 1. */
+int rt_denoise_albedo_device(rt_ctx* ctx, int width, int height, const float* d_radiance, const rt_hit* d_hits,
+                             const void* d_albedo, const rt_denoise_params* params, void* d_workspace,
+                             void* d_out_rgba, float* d_out_radiance, void* stream, double* ms);
+
 /* --------------------------------------------------------------- temporal -- */
 /* NON-REFERENCE: temporal accumulation that follows a moving camera.  The
  * previous frame's accumulated colour is reprojected through the first-hit
@@ -1035,7 +1086,17 @@ int rt_render_samples(rt_ctx* ctx, const rt_camera_ubo* cam, int width, int heig
  *                   whatever an earlier call left in the workspace
  *                   (tools/denoise_bench.py times a pass this way; the output
  *                   is meaningless); -1 (default) = every pass.  The same for
- *                   rt_denoise_history_device
+ *                   rt_denoise_history_device and rt_denoise_albedo_device
+ *   "denoise_albedo" NON-REFERENCE, 0 (default) / 1: rt_render_denoised filters
+ *                   the illumination: behind the hit buffer it runs
+ *                   rt_albedo_device into a buffer of the context (16 bytes per
+ *                   pixel more, grown on demand, freed by rt_destroy) and then
+ *                   rt_denoise_albedo_device in place of rt_denoise_device;
+ *                   stats->ms includes the albedo kernel's time.  With 0 the
+ *                   call enqueues what it always did.  Its refusals are the
+ *                   same either way
+ *   "denoise_albedo_used" (rt_get_option only) 1 when the last
+ *                   rt_render_denoised ran the albedo form
  *   "temporal_tile" rt_temporal_device's lane mapping: 1 = a wave on 64
  *                   consecutive pixels of a row, 2 = a wave on a 16x4 tile,
  *                   0 (default) = the one measured faster.

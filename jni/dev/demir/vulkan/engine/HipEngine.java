@@ -38,6 +38,7 @@ public class HipEngine implements Runnable {
     private volatile boolean denoise = false;                             // setDenoise: filter every frame
     private int dnIterations = 4, dnNormalPowerLog2 = 7;                  // rt_denoise_default_params
     private float dnSigmaDepth = 0.005f, dnSigmaColor = 0.5f;
+    private volatile boolean denoiseAlbedo = false;                       // setDenoiseAlbedo: filter the illumination
     private volatile boolean temporal = false;                            // setTemporal: accumulate across frames
     private int tpMaxHistory = 32;                                        // rt_temporal_default_params
     private float tpPlaneTol = 0.005f, tpNormalMin = 0.9f;
@@ -78,8 +79,12 @@ public class HipEngine implements Runnable {
     /** Filter every frame with the edge-avoiding denoiser (rt_render_denoised, its default parameters): the
      *  frames are then rendered synchronously, one at a time, instead of IN_FLIGHT at once. */
     public void setDenoise(boolean on) { denoise = on; }
+    /** With setDenoise: divide each frame by its first-hit albedo before the filter and multiply it back after
+     *  (rt option "denoise_albedo"), so that a surface's per-triangle albedos are not blurred with the noise. */
+    public void setDenoiseAlbedo(boolean on) { denoiseAlbedo = on; }
     /** One denoised frame of the given UBO into a direct RGBA8 buffer; on the render thread. */
     private void renderDenoised(ByteBuffer cameraUbo, ByteBuffer outRgba) {
+        HipNative.setOption(ctx, "denoise_albedo", denoiseAlbedo ? 1 : 0);
         HipNative.renderDenoised(ctx, cameraUbo, WIDTH, HEIGHT, MAX_BOUNCES, dnIterations, dnNormalPowerLog2,
                                  dnSigmaDepth, dnSigmaColor, outRgba);
     }
